@@ -8,7 +8,11 @@ driver launches one rank per GPU (torch.distributed, backend nccl = RCCL); chann
 no data-path collective and scaling is weak (one channel per GPU).  `--scatter` additionally times the RCCL
 scatter/gather of whole channels from rank 0 (reported in "extra", never in `value`).
 
-Prints ONE JSON line on rank 0.  The oracle (oracle/) is used only for the cpu_baseline leg and a parity spot check.
+Prints ONE JSON line on rank 0.  A plain run sets up, conditions and warms the device up, times the K steps, writes the
+last step's outputs when --dump-outputs is given, and prints the line.  Everything else the script measures or checks
+(the cold figure, the live counter passes, the whole-output and oracle parity checks, the comparison measurements under
+"extra" and the CPU baseline) runs only with --full.  The oracle (oracle/) is used only by --full: the cpu_baseline leg
+and a parity spot check.
 """
 import argparse
 import json
@@ -29,6 +33,9 @@ import __graft_entry__ as graft  # noqa: E402
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md chip table)
 BARRIER_COVER_STEPS = 40   # multi-rank runs: untimed passes of the step queued in front of the opening barrier (see main)
 VALU_PEAK_TFLOPS = 157.3   # FP32 vector peak, packed FMA counted
+DUMP_BYTES = 48 << 20      # --dump-outputs: the sampled indices and outputs of all channels together (64 MB at most)
+DUMP_EDGE = 4096           # --dump-outputs: first and last outputs of a step always written in full
+DUMP_SEED = 20261016       # --dump-outputs: seed of the sample in between
 
 WORKLOADS = {
     # name: (taps, decimation, log2 samples, description)
@@ -96,6 +103,34 @@ def whole_output_check(fir, f, taps, decim, x, y, n, i16, stream, device, calls,
 
 def algorithmic_flops_per_sample(taps, decim):
     return 4.0 * taps / decim         # real taps x complex data: 2 FMA = 4 flop per tap per OUTPUT sample
+
+
+def dump_index(m, channels):
+    """Complex output indices written by --dump-outputs: all m of them when they fit DUMP_BYTES, else the first and last
+    DUMP_EDGE and one seeded position in each of equal strata in between.  Sorted, unique, and the same in every run with
+    the same arguments; every channel is sampled at the same indices."""
+    k = DUMP_BYTES // (8 * (channels + 1))   # per index: itself as float64 + one complex float32 output per channel
+    if m <= k:
+        return np.arange(m, dtype=np.int64)
+    edge = min(DUMP_EDGE, k // 4)
+    inner, strata = m - 2 * edge, k - 2 * edge
+    lo = (np.arange(strata, dtype=np.int64) * inner) // strata
+    hi = (np.arange(1, strata + 1, dtype=np.int64) * inner) // strata
+    pick = lo + (np.random.default_rng(DUMP_SEED).random(strata) * (hi - lo)).astype(np.int64)
+    return np.concatenate([np.arange(edge, dtype=np.int64), edge + pick, np.arange(m - edge, m, dtype=np.int64)])
+
+
+def dump_outputs(out_dir, idx, outputs, rank):
+    """--dump-outputs: output_ch<c>.npy (float32, [len(idx), 2] = I, Q) for every channel this rank filtered, taken from
+    its output buffer as the timed path left it, and output_index.npy (float64) on rank 0."""
+    os.makedirs(out_dir, exist_ok=True)
+    if rank == 0:
+        np.save(os.path.join(out_dir, "output_index.npy"), idx.astype(np.float64))
+    idx_dev = None
+    for c, y in outputs:
+        if idx_dev is None:
+            idx_dev = torch.from_numpy(idx).to(y.device)
+        np.save(os.path.join(out_dir, "output_ch%d.npy" % c), y.view(-1, 2)[idx_dev].cpu().numpy().astype(np.float32))
 
 
 def cpu_baseline(taps_arr, decim, budget_s=10.0):
@@ -572,7 +607,7 @@ def main():
     ap.add_argument("--scatter-mc", action="store_true",
                     help="like --scatter through the library's own multi-channel front (if_fir_mc_*, in-library RCCL); "
                          "reported in \"extra\", never in `value`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (cpu_baseline)")
     ap.add_argument("--channels", type=int, default=None,
                     help="fixed TOTAL number of channels, channel c on rank c mod N, each rank filters its channels back "
                          "to back (BASELINE configs[3]: 8 channels on 8/4/2/1 GPUs; strong scaling).  Default: one "
@@ -582,15 +617,28 @@ def main():
     ap.add_argument("--condition-ms", type=float, default=300.0,
                     help="device time of untimed GPU work ahead of the warm-up steps (settled power state; see main)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not measure roofline.traffic in this run (two short rocprofv3 --pmc child passes ahead of the "
-                         "benchmark); the committed counter passes of profiles/traffic.json are quoted instead")
+                    help="with --full: do not measure roofline.traffic in this run (two short rocprofv3 --pmc child passes "
+                         "ahead of the benchmark); the committed counter passes of profiles/traffic.json are quoted instead, "
+                         "as in a run without --full")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the other single-GPU BASELINE configs timed after the headline (extra.configs)")
+                    help="with --full: skip the other single-GPU BASELINE configs timed after the headline (extra.configs)")
     ap.add_argument("--extras-first", action="store_true",
-                    help="development: run the comparison measurements (extra.*) between the two halves of the conditioning, "
-                         "ahead of the timed steps, as up to round 3 (A/B of the order: profiles/r04_bench_order.txt)")
+                    help="development (with --full): run the comparison measurements (extra.*) between the two halves of the "
+                         "conditioning, ahead of the timed steps, as up to round 3 (A/B of the order: profiles/r04_bench_order.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the cold figure, roofline.traffic from live "
+                         "counter passes, the whole-output and oracle parity checks, the comparison measurements (extra.*) and "
+                         "the CPU baseline.  Without it a run times the steps and prints the line, nothing more")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed: DIR/output_ch<c>.npy (float32 [k, 2], "
+                         "I and Q) per channel at the indices of DIR/output_index.npy (float64; all outputs, or a fixed "
+                         "seeded sample of at most 48 MiB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.extras_first and not args.full:
+        ap.error("--extras-first orders the comparison measurements of --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not under a launcher: become the launcher (child process; nothing here has touched the GPU yet)
@@ -609,7 +657,7 @@ def main():
     # roofline.traffic measured on THIS box in THIS run: profiler passes of a short child run, before
     # this process touches the GPU.  One GPU only (the children use device 0); any failure falls back to the committed passes.
     live = None
-    if world == 1 and not args.no_live_traffic and not args.channels and args.variant is None:
+    if args.full and world == 1 and not args.no_live_traffic and not args.channels and args.variant is None:
         try:
             live = live_traffic(args.workload, args.backend)
         except Exception:   # noqa: BLE001 - never fatal
@@ -693,8 +741,9 @@ def main():
 
     # ---- the COLD figure: the driver's own W warm-up + K steps right away, before any conditioning ------
     # Reported beside `value` (roofline.cold_*), never as `value`: what a caller sees who starts filtering on an idle chip.
+    # (--full only)
     cold_ms = None
-    if args.condition_ms > 0:
+    if args.full and args.condition_ms > 0:
         for _ in range(args.warmup):
             step_stream()
         c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -868,26 +917,32 @@ def main():
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max, dev_ms_max, cold_ms_max = float(t[0].item()), float(t[1].item()), float(t[2].item())
+    if args.dump_outputs:
+        # before anything else runs on these buffers (the direct-form comparison of --full filters into y again)
+        dump_outputs(args.dump_outputs, dump_index(m, total_channels),
+                     [(channel, y)] + [(c, yc) for c, (_, _, yc) in zip(owned[1:], more)], rank)
 
-    # whole-output check of the TIMED context's last step against a different kernel family in the same stream state
-    # (a work-distribution bug that leaves blocks unwritten makes a launch look fast; windows do not see it)
-    whole = whole_output_check(fir, f, taps, decim, x, y, n, i16, stream, local_rank,
-                               cold_passes + cond_passes + args.warmup + args.steps, names, nco)
-    if use_dist:
-        okt = torch.tensor([1.0 if whole["ok"] else 0.0], dtype=torch.float64, device=dev)
-        dist.all_reduce(okt, op=dist.ReduceOp.MIN)
-        whole["ok_all_ranks"] = bool(okt.item() > 0.5)
-    if not whole.get("ok_all_ranks", whole["ok"]):
-        if rank == 0:
-            os.write(json_fd, (json.dumps({"metric": "complex-IQ MSamples/s through %d-tap FIR" % taps_n, "value": None,
-                                           "error": "timed output failed the whole-output parity check",
-                                           "parity": {"whole_output": whole}}) + "\n").encode())
-        f.close()
+    whole = None
+    if args.full:
+        # whole-output check of the TIMED context's last step against a different kernel family in the same stream state
+        # (a work-distribution bug that leaves blocks unwritten makes a launch look fast; windows do not see it)
+        whole = whole_output_check(fir, f, taps, decim, x, y, n, i16, stream, local_rank,
+                                   cold_passes + cond_passes + args.warmup + args.steps, names, nco)
         if use_dist:
-            dist.destroy_process_group()
-        sys.exit(1)
-    if not args.extras_first:
-        measure_extras()
+            okt = torch.tensor([1.0 if whole["ok"] else 0.0], dtype=torch.float64, device=dev)
+            dist.all_reduce(okt, op=dist.ReduceOp.MIN)
+            whole["ok_all_ranks"] = bool(okt.item() > 0.5)
+        if not whole.get("ok_all_ranks", whole["ok"]):
+            if rank == 0:
+                os.write(json_fd, (json.dumps({"metric": "complex-IQ MSamples/s through %d-tap FIR" % taps_n, "value": None,
+                                               "error": "timed output failed the whole-output parity check",
+                                               "parity": {"whole_output": whole}}) + "\n").encode())
+            f.close()
+            if use_dist:
+                dist.destroy_process_group()
+            sys.exit(1)
+        if not args.extras_first:
+            measure_extras()
     if args.scatter and use_dist:
         cs = pkg.channel_shard
         root_inputs = None
@@ -990,33 +1045,35 @@ def main():
                 traffic_src = ("NOT measured in this run: TCC counters of kernel %s from the committed rocprofv3 "
                                "passes profiles/%s_* (another box), file profiles/traffic.json"
                                % (rec.get("kernel"), rec.get("round")))
-        # parity spot check (oracle as checker only): first 4096 outputs of this rank's last step vs the order model.
-        # the stream was continued for warmup+steps calls, so regenerate the expected state cheaply: only check that
-        # a fresh context reproduces the oracle on the head of the stream.
-        oracle = graft.load_oracle()
-        f2 = fir.IfFir(taps, decim, 0, device=local_rank, backend=backend_ids[args.backend])
-        f2.set_stream(stream.cuda_stream)
-        if i16:
-            f2.set_input_format(fir.INPUT_I16)
-        if args.variant is not None:
-            f2.set_tuning(args.variant)
-        if nco:
-            f2.set_nco(nco)
-        head = 1 << 16
-        yh = torch.empty(2 * f2.out_count(head), dtype=torch.float32, device=dev)
-        f2.process_device(x.data_ptr(), yh.data_ptr(), head)
-        torch.cuda.synchronize()
-        xh = x[:2 * head].cpu().numpy()
-        if i16:
-            xh = xh.astype(np.float32) * np.float32(2.0 ** -15)
-        ref64 = oracle.fir_nco_f64(taps, xh, decim, oracle.nco_phase_word(nco)) if nco else oracle.fir_f64(taps, xh, decim)
-        l2, mx = oracle.err_metrics(yh.cpu().numpy(), ref64)
-        parity = {"rel_l2_vs_f64_oracle": l2, "rel_max_vs_f64_oracle": mx, "tolerance": 1e-6,
-                  "window": "first 2^16 input samples", "whole_output": whole}
-        if f2.get_backend() in (fir.BACKEND_HIP_DIRECT, fir.BACKEND_HIP_GENERIC) and not nco:
-            model = oracle.fir_f32fma(taps, xh, decim, seg_mode=1, seg_len=32)
-            parity["bit_exact_vs_f32_order_model"] = bool(np.array_equal(yh.cpu().numpy(), model))
-        f2.close()
+        parity = None
+        if args.full:
+            # parity spot check (oracle as checker only): first 4096 outputs of this rank's last step vs the order model.
+            # the stream was continued for warmup+steps calls, so regenerate the expected state cheaply: only check that
+            # a fresh context reproduces the oracle on the head of the stream.
+            oracle = graft.load_oracle()
+            f2 = fir.IfFir(taps, decim, 0, device=local_rank, backend=backend_ids[args.backend])
+            f2.set_stream(stream.cuda_stream)
+            if i16:
+                f2.set_input_format(fir.INPUT_I16)
+            if args.variant is not None:
+                f2.set_tuning(args.variant)
+            if nco:
+                f2.set_nco(nco)
+            head = 1 << 16
+            yh = torch.empty(2 * f2.out_count(head), dtype=torch.float32, device=dev)
+            f2.process_device(x.data_ptr(), yh.data_ptr(), head)
+            torch.cuda.synchronize()
+            xh = x[:2 * head].cpu().numpy()
+            if i16:
+                xh = xh.astype(np.float32) * np.float32(2.0 ** -15)
+            ref64 = oracle.fir_nco_f64(taps, xh, decim, oracle.nco_phase_word(nco)) if nco else oracle.fir_f64(taps, xh, decim)
+            l2, mx = oracle.err_metrics(yh.cpu().numpy(), ref64)
+            parity = {"rel_l2_vs_f64_oracle": l2, "rel_max_vs_f64_oracle": mx, "tolerance": 1e-6,
+                      "window": "first 2^16 input samples", "whole_output": whole}
+            if f2.get_backend() in (fir.BACKEND_HIP_DIRECT, fir.BACKEND_HIP_GENERIC) and not nco:
+                model = oracle.fir_f32fma(taps, xh, decim, seg_mode=1, seg_len=32)
+                parity["bit_exact_vs_f32_order_model"] = bool(np.array_equal(yh.cpu().numpy(), model))
+            f2.close()
         line = {
             "metric": "complex-IQ MSamples/s through %d-tap FIR" % taps_n,
             "value": round(value, 1), "unit": "MSamples/s",
@@ -1030,7 +1087,7 @@ def main():
                        "device": f.device_info()},
             "conditioning": {"device_ms": round(conditioning_ms, 1), "extra_passes_of_the_step": cond_passes,
                              "passes_covering_the_opening_barrier": BARRIER_COVER_STEPS if use_dist else 0,
-                             "extras_order": "before" if args.extras_first else "after",
+                             "extras_order": "before" if args.extras_first else ("after" if args.full else "none"),
                              "note": "untimed GPU work ahead of the W warm-up steps: passes of the same step (and, only with "
                                      "--extras-first = extras_order 'before', the comparison measurements, as in the records up to "
                                      "round 3; since round 4 they run BEHIND the timed steps, which alone moves `value` by about "
@@ -1059,11 +1116,12 @@ def main():
                      "note": ("direct-form-EQUIVALENT rate (4*taps/decimation flop per input sample / time); the "
                               "overlap-save kernel executes ~8x fewer flops, so this is not a VALU utilisation")
                      if f.get_backend() == fir.BACKEND_HIP_FFT else "executed FP32 VALU flops / time"},
-            "parity": parity,
         }
+        if parity is not None:
+            line["parity"] = parity
         if extra:
             line["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(taps, decim)
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     f.close()

@@ -97,3 +97,27 @@ def test_multi_gpu_check_record_schema_and_bytes():
     assert rec["bytes_through_send_recv"] == 7 * n * 8 + 7 * (n // 4) * 8 + 28
     rec = bench.multi_gpu_check_record(2, 3, 1000, 255, 4, "x", [[1.0, 2.0]], [True, False, True])
     assert rec["ok"] is False
+
+
+def test_dump_index_is_fixed_sorted_and_within_budget():
+    """--dump-outputs writes the last step's outputs at these indices: the same ones in every run, inside the output,
+    unique, with the first and last outputs of the step, and with the outputs of all channels within the 64 MB limit."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_for_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert np.array_equal(bench.dump_index(1000, 1), np.arange(1000))
+    for m, channels in ((1 << 26, 1), (1 << 28, 1), (1 << 26, 8), (3 << 20, 1), ((3 << 20) + 1, 1), (1 << 26, 4000)):
+        idx = bench.dump_index(m, channels)
+        assert np.array_equal(idx, bench.dump_index(m, channels))
+        assert idx[0] == 0 and idx[-1] == m - 1 and (np.diff(idx) > 0).all()
+        assert idx.size * 8 * (channels + 1) <= min(bench.DUMP_BYTES, 64 << 20)
+        assert idx.size >= bench.DUMP_BYTES // (8 * (channels + 1)) - 1
+
+
+def test_extras_first_needs_full():
+    p = run_bench("--extras-first", "--dry-run")
+    assert p.returncode != 0 and "--full" in p.stderr and not p.stdout.strip()
+    p = run_bench("--steps", "0", "--dry-run")
+    assert p.returncode != 0 and not p.stdout.strip()

@@ -21,8 +21,8 @@ timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_dri
 step "result table"
 timeout -k 10 900 bash tools/bench_all.sh ${TAG}_all
 step "configs[3] on one GPU: 8 channels x 255 taps, /4 and D=1"
-timeout -k 10 300 python3 bench.py --channels 8 --gpus 1 --no-cpu-baseline --no-extra-configs > $O/bench_8channels_1gpu_dec4.json 2> /dev/null; tail -1 $O/bench_8channels_1gpu_dec4.json | cut -c1-200
-timeout -k 10 300 python3 bench.py --channels 8 --gpus 1 --workload fir255_2p28 --no-cpu-baseline --no-extra-configs > $O/bench_8channels_1gpu_d1.json 2> /dev/null; tail -1 $O/bench_8channels_1gpu_d1.json | cut -c1-200
+timeout -k 10 300 python3 bench.py --full --channels 8 --gpus 1 --no-cpu-baseline --no-extra-configs > $O/bench_8channels_1gpu_dec4.json 2> /dev/null; tail -1 $O/bench_8channels_1gpu_dec4.json | cut -c1-200
+timeout -k 10 300 python3 bench.py --full --channels 8 --gpus 1 --workload fir255_2p28 --no-cpu-baseline --no-extra-configs > $O/bench_8channels_1gpu_d1.json 2> /dev/null; tail -1 $O/bench_8channels_1gpu_d1.json | cut -c1-200
 step "AUTO policy sweep (2^27 samples)"
 IF_FIR_DEBUG=1 timeout -k 10 600 python3 tools/policy_sweep.py 27 > $O/policy_sweep.txt 2>&1; tail -5 $O/policy_sweep.txt | cut -c1-200
 step "memory floor and sustained run on this box"

@@ -7,7 +7,7 @@ O=gpurun_out/$1
 mkdir -p $O
 for k in 1 2 3 4; do
   for mode in "" "--extras-first"; do
-    timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 $mode > $O/b.json 2> $O/b.err || { echo "bench failed"; tail -3 $O/b.err; exit 1; }
+    timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full $mode > $O/b.json 2> $O/b.err || { echo "bench failed"; tail -3 $O/b.err; exit 1; }
     python3 - "$mode" $O/b.json <<'PY' | tee -a $O/bench_order.txt
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
