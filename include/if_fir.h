@@ -225,6 +225,47 @@ uint8_t if_fir_mc_get_chunk_samples(const if_fir_mc_ctx_t *pCtx, uint64_t *pullC
 if_fir_ctx_t *if_fir_mc_channel_ctx(if_fir_mc_ctx_t *pCtx, uint32_t ulChannel);
 const char *if_fir_mc_last_error(const if_fir_mc_ctx_t *pCtx);
 
+/* ---- interpolator (docs/SPEC.md §6; BUILD-DEFINED) ---------------------------------------------------------------------
+ * The transmit direction: upsample by L (1..64), filter, and optionally mix UP:
+ *     u[n] = x[n/L] if n mod L == 0, else 0;   y[n] = sum_k h[k] u[n-k];   y'[n] = exp(+j*2*pi*P*n/2^32) y[n]
+ * n = absolute OUTPUT index since init/reset.  A call with N input samples emits exactly N*L outputs (no phase is carried:
+ * process(a||b) == process(a); process(b)).  Taps are used as given: image-rejection taps need a gain of L.  Real or complex
+ * taps, T <= 4096; float32 or int16 input (if_fir_interp_set_input_format); float32 I/Q output.
+ * Backends: IF_FIR_BACKEND_HIP_FFT (AUTO's pick for L in {1, 2, 4, ..., 64} and T <= 3073: overlap-save) and
+ * IF_FIR_BACKEND_HIP_GENERIC (any L and T: one output per thread); others are refused.  Errors: 0 + if_fir_interp_last_error();
+ * the context stays usable.  Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_interp if_fir_interp_t;
+#define IF_FIR_MAX_INTERPOLATION 64u
+
+uint8_t if_fir_interp_init(if_fir_interp_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulInterpolation,
+                           uint64_t ullMaxSamples, int32_t lDevice);
+/* complex taps: ulTaps interleaved (re, im) pairs */
+uint8_t if_fir_interp_init_complex(if_fir_interp_t **ppCtx, const float *pfTapsIQ, uint32_t ulTaps, uint32_t ulInterpolation,
+                                   uint64_t ullMaxSamples, int32_t lDevice);
+void if_fir_interp_destroy(if_fir_interp_t *pCtx);
+/* zero the history and the output index */
+uint8_t if_fir_interp_reset(if_fir_interp_t *pCtx);
+uint8_t if_fir_interp_set_backend(if_fir_interp_t *pCtx, uint32_t ulBackend);
+uint32_t if_fir_interp_get_backend(const if_fir_interp_t *pCtx); /* the resolved (non-AUTO) backend */
+uint8_t if_fir_interp_set_input_format(if_fir_interp_t *pCtx, uint32_t ulFormat);
+/* NCO as an UP-mix of the output: y'[n] = exp(+j*2*pi*f*n) y[n], n = absolute output index (mod 2^32), f quantised to a 32-bit
+ * phase word as in if_fir_set_nco.  Note the sign: if_fir_set_nco mixes the decimator's INPUT DOWN with exp(-j*2*pi*f*a).
+ * |dFreq| <= 0.5; 0 switches it off; takes effect from the next call as if set since the last reset. */
+uint8_t if_fir_interp_set_nco(if_fir_interp_t *pCtx, double dFreq);
+uint8_t if_fir_interp_get_nco(const if_fir_interp_t *pCtx, double *pdFreq);
+uint8_t if_fir_interp_set_stream(if_fir_interp_t *pCtx, void *pStream);
+uint8_t if_fir_interp_synchronize(if_fir_interp_t *pCtx);
+const char *if_fir_interp_last_error(const if_fir_interp_t *pCtx);
+/* = ullSamples * L */
+uint64_t if_fir_interp_out_count(const if_fir_interp_t *pCtx, uint64_t ullSamples);
+/* host pointers, synchronous; ullSamples <= ullMaxSamples of init; pfIQOut holds ullSamples * L samples */
+uint8_t if_fir_interp_process(if_fir_interp_t *pCtx, const void *pIQIn, float *pfIQOut, uint64_t ullSamples,
+                              uint64_t *pullOutSamples);
+/* device pointers, asynchronous on the context's stream.  Overlap-save backend: aligned to one sample (input 8 bytes, 4 for
+ * int16; output 8 bytes); generic backend: 16 bytes.  pDevOut holds ullSamples * L samples. */
+uint8_t if_fir_interp_process_device(if_fir_interp_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples,
+                                     uint64_t *pullOutSamples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,17 @@ uint32_t if_fir_mc_debug_plan(uint32_t ulWorld, uint32_t ulChannels, uint32_t ul
                               uint32_t ulInBytes, uint32_t ulTaps, uint32_t ulDecimation, uint64_t ullConsumed,
                               uint64_t ullChunk, uint64_t *pullOut, uint32_t ulMaxOps);
 
+/* interpolator (if_fir_interp_t): bForceFull = 1 runs the overlap-save kernel's full form (4096-point forward transform of the
+ * zero-stuffed block) for every L instead of the small form (L >= 4); ulGridLimit = at most this many workgroups (0 = the
+ * launcher's choice; same results: small inputs then take several rounds of the persistent workgroups) */
+uint8_t if_fir_debug_interp_config(if_fir_interp_t *pCtx, uint32_t bForceFull, uint32_t ulGridLimit);
+/* interpolator: set the count of input samples consumed since reset (the output index of the next call is ullSamples * L; the
+ * history is kept): lets a test reach output indices past 2^32 without streaming them */
+uint8_t if_fir_debug_interp_seek(if_fir_interp_t *pCtx, uint64_t ullSamples);
+/* host-only: the interpolator's multiply table H[k] = FFT_4096(taps)[k] / 4096 as 4096 (re, im) pairs (ulOutFloats >= 8192);
+ * returns the floats written, 0 when the taps are not served by the overlap-save kernel */
+uint32_t if_fir_debug_interp_tables(const float *pfTaps, uint32_t ulTaps, uint32_t bComplexTaps, float *pfOut, uint32_t ulOutFloats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,400 @@
+// if_fir_interp.hip — interpolate-by-L FIR with a fused NCO up-mix for gfx950 (docs/SPEC.md §6).
+//
+//   u[n] = x[n/L] (n mod L == 0, else 0),   y[n] = sum_k h[k] u[n-k],   y'[n] = exp(+j 2 pi P n / 2^32) y[n]
+//
+// fir_interp_kernel (overlap-save, L | 64, T <= 3073): one WORKGROUP = one block of 4096 output-rate points in LDS.  The
+// block starts OVL = 64 ROWS outputs before the first output it keeps and advances A = 4096 - OVL outputs = A/L inputs;
+// L divides 64, so every block starts on an input sample.
+//   small form (L >= 4)  load the block's 4096/L input samples, 4096/L-point forward transform; the transform of the
+//                        zero-stuffed block is that one repeated L times, so the multiply by H reads it modulo 4096/L
+//   full form (any L)    load the zero-stuffed block, 4096-point forward transform (the small form's cross-check)
+// then Z = H X (fused into the first inverse pass), the 4096-point inverse, and the store of positions OVL..4095 fused
+// into the last inverse pass (rotated by the NCO).  Transforms: radix-4 Stockham passes (one radix-2 pass first when the
+// size is an odd power of 2) with the twiddles W4096^i from a table; index algebra in tools/fft_model.py (interp_block).
+// fir_interp_generic_kernel: one output per thread, all the taps of its phase; any L, any T (the slow cross-check).
+//
+// Build: compiled once per overlap length (-DIF_FIR_INTERP_ROWS=4|8|16|32|48, the overlap-save instantiations and their
+// launcher) and once without (host tables, routing, the generic kernel).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <atomic>
+#include <cmath>
+
+#include "if_fir_interp.h"
+#include "if_fir_kernels.h"
+
+// LDS reads as single ds_read_b64, as in the decimator's overlap-save units (if_fir_fft_dev.h, IF_FIR_LDS_SINGLE_READS): the
+// machine-level pairing is switched off per kernel here, the IR-level vectorizer for the whole unit (csrc/Makefile, NOPAIR)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define IF_FIR_INTERP_SINGLE_READS __attribute__((target("no-load-store-opt")))
+#else
+#define IF_FIR_INTERP_SINGLE_READS
+#endif
+
+namespace if_fir
+{
+
+constexpr int INTERP_THREADS = 256;
+
+__device__ __forceinline__ float2 ip_cmul(float2 a, float2 b)
+{
+    return make_float2(fmaf(a.x, b.x, -a.y * b.y), fmaf(a.x, b.y, a.y * b.x));
+}
+
+__device__ __forceinline__ float2 ip_cvt_i16(int w)
+{
+    return make_float2((float)(short)(w & 0xffff) * (1.0f / 32768.0f), (float)(w >> 16) * (1.0f / 32768.0f));
+}
+
+// input sample j of this call (float32): j < 0 from the history (hist[hist_len + j]), j >= N reads 0
+template <bool I16>
+__device__ __forceinline__ float2 ip_load(const void *__restrict__ in, const float2 *__restrict__ hist, int hist_len, int64_t N,
+                                          int64_t j)
+{
+    if (j < 0)
+        return (j + hist_len >= 0) ? hist[j + hist_len] : make_float2(0.f, 0.f);
+    if (j >= N)
+        return make_float2(0.f, 0.f);
+    if constexpr (I16)
+        return ip_cvt_i16(static_cast<const int *>(in)[j]);
+    else
+        return static_cast<const float2 *>(in)[j];
+}
+
+// the next call's history = the last hist_len samples of (history || input), converted to float32; written by workgroup 0
+// into the other ping-pong buffer (everything it reads is read-only during the launch)
+template <bool I16>
+__device__ __forceinline__ void ip_write_history(const void *__restrict__ in, const float2 *__restrict__ hist, float2 *__restrict__ hist_out,
+                                                 int hist_len, int64_t N)
+{
+    if (blockIdx.x != 0 || !hist_out)
+        return;
+    for (int i = threadIdx.x; i < hist_len; i += blockDim.x)
+        hist_out[i] = ip_load<I16>(in, hist, hist_len, N, N - hist_len + i);
+}
+
+#if !defined(IF_FIR_INTERP_ROWS) // ================= host side + the generic kernel =================
+
+bool interp_fft_supported(int T, int L)
+{
+    return T >= 1 && T <= INTERP_FFT_MAX_TAPS && L >= 1 && L <= INTERP_MAX_L && (64 % L) == 0;
+}
+
+int interp_overlap_rows(int T)
+{
+    const int rows[] = {4, 8, 16, 32, 48};
+    for (int r : rows)
+        if (64 * r >= T - 1)
+            return r;
+    return 48;
+}
+
+int interp_hist_len(int T, int L)
+{
+    // the overlap-save kernel reads OVL / L samples before a block; the generic kernel ceil((T - 1) / L): one length serves both
+    const int ovl = T <= INTERP_FFT_MAX_TAPS ? 64 * interp_overlap_rows(T) : T - 1;
+    return (ovl + L - 1) / L;
+}
+
+void interp_build_tables(const float *taps, int T, int ctaps, float2 *H, float2 *tw)
+{
+    double c[INTERP_N], s[INTERP_N];
+    for (int i = 0; i < INTERP_N; i++)
+    {
+        c[i] = cos(2.0 * M_PI * i / INTERP_N);
+        s[i] = -sin(2.0 * M_PI * i / INTERP_N);
+        tw[i] = make_float2((float)c[i], (float)s[i]);
+    }
+    for (int k = 0; k < INTERP_N; k++)
+    {
+        double re = 0.0, im = 0.0;
+        for (int t = 0; t < T; t++)
+        {
+            const double hr = ctaps ? taps[2 * t] : taps[t], hi = ctaps ? taps[2 * t + 1] : 0.0;
+            const int e = (int)(((int64_t)k * t) & (INTERP_N - 1));
+            re += hr * c[e] - hi * s[e];
+            im += hr * s[e] + hi * c[e];
+        }
+        H[k] = make_float2((float)(re / INTERP_N), (float)(im / INTERP_N));
+    }
+}
+
+hipError_t launch_interp_fft(const InterpArgs &a)
+{
+    if (!interp_fft_supported(a.T, a.L) || !a.H || !a.tw)
+        return hipErrorInvalidConfiguration;
+    switch (interp_overlap_rows(a.T))
+    {
+    case 4: return launch_interp_fft_rows<4>(a);
+    case 8: return launch_interp_fft_rows<8>(a);
+    case 16: return launch_interp_fft_rows<16>(a);
+    case 32: return launch_interp_fft_rows<32>(a);
+    default: return launch_interp_fft_rows<48>(a);
+    }
+}
+
+template <bool I16, bool CT, bool NCO>
+__global__ __launch_bounds__(INTERP_THREADS) void fir_interp_generic_kernel(const void *__restrict__ in, float2 *__restrict__ out,
+                                                                           const float2 *__restrict__ hist, float2 *__restrict__ hist_out,
+                                                                           int hist_len, const float *__restrict__ taps, int T, int L,
+                                                                           int64_t N, int64_t M, uint32_t nco_word, uint32_t nco_phi0)
+{
+    ip_write_history<I16>(in, hist, hist_out, hist_len, N);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride)
+    {
+        // output i of the call has phase i mod L (every call starts on a multiple of L); tap k meets input (i - k) / L
+        // (partial sums of 32 taps added into the total with a compensated (two-sum) addition: one running float32 sum over
+        // 3000 taps drifts past the SPEC tolerance)
+        float ar = 0.f, ai = 0.f, cr = 0.f, ci = 0.f;
+        int k = (int)(i % L);
+        while (k < T)
+        {
+            float pr = 0.f, pi = 0.f;
+            for (int c = 0; c < 32 && k < T; c++, k += L)
+            {
+                const float2 x = ip_load<I16>(in, hist, hist_len, N, (i - k) / L);
+                if constexpr (CT)
+                {
+                    const float hr = taps[2 * k], hi = taps[2 * k + 1];
+                    pr = fmaf(hr, x.x, fmaf(-hi, x.y, pr));
+                    pi = fmaf(hr, x.y, fmaf(hi, x.x, pi));
+                }
+                else
+                {
+                    const float h = taps[k];
+                    pr = fmaf(h, x.x, pr);
+                    pi = fmaf(h, x.y, pi);
+                }
+            }
+            const float sr = ar + pr, si = ai + pi;
+            const float br = sr - ar, bi = si - ai;
+            cr += (ar - (sr - br)) + (pr - br);
+            ci += (ai - (si - bi)) + (pi - bi);
+            ar = sr;
+            ai = si;
+        }
+        ar += cr;
+        ai += ci;
+        float2 y = make_float2(ar, ai);
+        if constexpr (NCO)
+            y = ip_cmul(y, nco_phasor(nco_phi0 + nco_word * (uint32_t)i));
+        out[i] = y;
+    }
+}
+
+template <bool I16, bool CT, bool NCO>
+static hipError_t launch_generic_t(const InterpArgs &a)
+{
+    int64_t groups = (a.M + INTERP_THREADS - 1) / INTERP_THREADS;
+    if (groups < 1)
+        groups = 1; // (the history is written even by a call without outputs)
+    if (groups > 65536)
+        groups = 65536;
+    if (a.grid_limit > 0 && groups > a.grid_limit)
+        groups = a.grid_limit;
+    hipLaunchKernelGGL((fir_interp_generic_kernel<I16, CT, NCO>), dim3((unsigned)groups), dim3(INTERP_THREADS), 0, a.stream, a.in,
+                       static_cast<float2 *>(a.out), a.hist, a.hist_out, a.hist_len, a.taps, a.T, a.L, a.N, a.M, a.nco_word,
+                       a.nco_phi0);
+    return hipGetLastError();
+}
+
+hipError_t launch_interp_generic(const InterpArgs &a)
+{
+    const bool nco = a.nco_word != 0;
+    if (a.in_i16)
+    {
+        if (a.ctaps)
+            return nco ? launch_generic_t<true, true, true>(a) : launch_generic_t<true, true, false>(a);
+        return nco ? launch_generic_t<true, false, true>(a) : launch_generic_t<true, false, false>(a);
+    }
+    if (a.ctaps)
+        return nco ? launch_generic_t<false, true, true>(a) : launch_generic_t<false, true, false>(a);
+    return nco ? launch_generic_t<false, false, true>(a) : launch_generic_t<false, false, false>(a);
+}
+
+#else // ================= overlap-save kernel: one unit per overlap length =================
+
+// radix-R butterfly; forward = exp(-j ...), INV = exp(+j ...)
+template <int R, bool INV>
+__device__ __forceinline__ void ip_bfly(float2 (&v)[R])
+{
+    if constexpr (R == 2)
+    {
+        const float2 a = v[0], b = v[1];
+        v[0] = make_float2(a.x + b.x, a.y + b.y);
+        v[1] = make_float2(a.x - b.x, a.y - b.y);
+    }
+    else
+    {
+        const float2 t0 = make_float2(v[0].x + v[2].x, v[0].y + v[2].y), t1 = make_float2(v[0].x - v[2].x, v[0].y - v[2].y);
+        const float2 t2 = make_float2(v[1].x + v[3].x, v[1].y + v[3].y), t3 = make_float2(v[1].x - v[3].x, v[1].y - v[3].y);
+        // -j t3 (forward) / +j t3 (inverse)
+        const float2 m = INV ? make_float2(-t3.y, t3.x) : make_float2(t3.y, -t3.x);
+        v[0] = make_float2(t0.x + t2.x, t0.y + t2.y);
+        v[2] = make_float2(t0.x - t2.x, t0.y - t2.y);
+        v[1] = make_float2(t1.x + m.x, t1.y + m.y);
+        v[3] = make_float2(t1.x - m.x, t1.y - m.y);
+    }
+}
+
+// One Stockham pass over nf points (tools/fft_model.py, stockham): j = 0 .. nf/R - 1, k = j mod ns,
+//   v[r] = src(j + r nf/R) W_{ns R}^(r k),  V = DFT_R(v),  dst((j - k) R + k + r ns, V[r]).
+// Every input is read before the workgroup barrier, every output written after it: src and dst may be the same LDS buffer.
+template <int R, bool INV, class Src, class Dst>
+__device__ __forceinline__ void ip_pass(int nf, int ns, const float2 *__restrict__ tw, Src src, Dst dst)
+{
+    constexpr int Q = INTERP_N / 4 / INTERP_THREADS; // j per thread at most (nf / R <= 1024)
+    const int nr = nf / R;
+    float2 v[Q][R];
+#pragma unroll
+    for (int q = 0; q < Q; q++)
+    {
+        const int j = (int)threadIdx.x + q * INTERP_THREADS;
+        if (j < nr)
+#pragma unroll
+            for (int r = 0; r < R; r++)
+                v[q][r] = src(j + r * nr);
+    }
+    __syncthreads();
+    const int tstep = INTERP_N / (ns * R);
+#pragma unroll
+    for (int q = 0; q < Q; q++)
+    {
+        const int j = (int)threadIdx.x + q * INTERP_THREADS;
+        if (j < nr)
+        {
+            const int k = j & (ns - 1);
+            if (ns > 1)
+#pragma unroll
+                for (int r = 1; r < R; r++)
+                {
+                    float2 w = tw[(unsigned)(r * k * tstep)];
+                    if (INV)
+                        w.y = -w.y;
+                    v[q][r] = ip_cmul(v[q][r], w);
+                }
+            ip_bfly<R, INV>(v[q]);
+            const int base = (j - k) * R + k;
+#pragma unroll
+            for (int r = 0; r < R; r++)
+                dst(base + r * ns, v[q][r]);
+        }
+    }
+    __syncthreads();
+}
+
+// (single ds_read_b64 LDS reads, like the decimator's overlap-save units)
+template <int OVL_ROWS, bool I16, bool NCO, bool SMALL>
+__global__ __launch_bounds__(INTERP_THREADS, 2) IF_FIR_INTERP_SINGLE_READS void fir_interp_kernel(
+    const void *__restrict__ in, float2 *__restrict__ out, const float2 *__restrict__ hist, float2 *__restrict__ hist_out, int hist_len,
+    const float2 *__restrict__ H, const float2 *__restrict__ tw, int L, int64_t N, int64_t M, int64_t nblocks, uint32_t nco_word,
+    uint32_t nco_phi0)
+{
+    constexpr int OVL = 64 * OVL_ROWS;
+    constexpr int A = INTERP_N - OVL; // kept outputs per block
+    __shared__ float2 buf[INTERP_N];
+    ip_write_history<I16>(in, hist, hist_out, hist_len, N);
+    const int nf = SMALL ? INTERP_N / L : INTERP_N; // forward transform size
+    const int a_in = A / L;                          // input samples per block advance
+    const int ovl_in = OVL / L;
+    auto lds = [&](int i) -> float2 { return buf[i]; };
+    auto to_lds = [&](int i, float2 v) { buf[i] = v; };
+    for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x)
+    {
+        const int64_t j0 = b * a_in - ovl_in; // input index of the block's first point
+        const int64_t o0 = b * A - OVL;       // output index of the block's first point
+        // ---- the block's input into LDS (the full form zero-stuffed), then the forward transform ----
+        for (int p = threadIdx.x; p < nf; p += INTERP_THREADS)
+        {
+            if (SMALL)
+                buf[p] = ip_load<I16>(in, hist, hist_len, N, j0 + p);
+            else
+                buf[p] = (p & (L - 1)) == 0 ? ip_load<I16>(in, hist, hist_len, N, j0 + p / L) : make_float2(0.f, 0.f);
+        }
+        __syncthreads();
+        int ns = 1;
+        if (nf & 0x2aaa) // log2(nf) odd: one radix-2 pass first
+        {
+            ip_pass<2, false>(nf, ns, tw, lds, to_lds);
+            ns = 2;
+        }
+#pragma unroll 1
+        for (; ns < nf; ns *= 4)
+            ip_pass<4, false>(nf, ns, tw, lds, to_lds);
+        // ---- Z = H X (X read modulo nf), fused into the first inverse pass; 1/4096 is in H ----
+        auto zsrc = [&](int k) -> float2 { return ip_cmul(H[(unsigned)k], buf[k & (nf - 1)]); };
+        ip_pass<4, true>(INTERP_N, 1, tw, zsrc, to_lds);
+#pragma unroll 1
+        for (ns = 4; ns < INTERP_N / 4; ns *= 4)
+            ip_pass<4, true>(INTERP_N, ns, tw, lds, to_lds);
+        // ---- last inverse pass: positions OVL..4095 straight to the outputs (rotated by the NCO); beyond M dropped ----
+        float2 *ob = out + o0;                                  // (wave-uniform base: 32-bit offsets below)
+        const int pend = M - o0 < INTERP_N ? (int)(M - o0) : INTERP_N; // positions past the last output are dropped
+        const uint32_t phb = nco_phi0 + nco_word * (uint32_t)o0;
+        auto store = [&](int p, float2 v) {
+            if (p >= OVL && p < pend)
+            {
+                if constexpr (NCO)
+                    v = ip_cmul(v, nco_phasor(phb + nco_word * (uint32_t)p));
+                ob[(unsigned)p] = v;
+            }
+        };
+        ip_pass<4, true>(INTERP_N, INTERP_N / 4, tw, lds, store);
+    }
+}
+
+template <int ROWS, bool I16, bool NCO, bool SMALL>
+static hipError_t launch_t(const InterpArgs &a, int64_t nblocks, int groups)
+{
+    hipLaunchKernelGGL((fir_interp_kernel<ROWS, I16, NCO, SMALL>), dim3((unsigned)groups), dim3(INTERP_THREADS), 0, a.stream, a.in,
+                       static_cast<float2 *>(a.out), a.hist, a.hist_out, a.hist_len, a.H, a.tw, a.L, a.N, a.M, nblocks, a.nco_word,
+                       a.nco_phi0);
+    return hipGetLastError();
+}
+
+template <int ROWS>
+hipError_t launch_interp_fft_rows(const InterpArgs &a)
+{
+    constexpr int A = INTERP_N - 64 * ROWS;
+    const int64_t nblocks = (a.M + A - 1) / A;
+    // persistent workgroups, two per CU (up to 256 VGPRs per lane: two waves per SIMD); at least one, which writes the history
+    static std::atomic<int> cus[MAX_DEVICES];
+    if (a.device < 0 || a.device >= MAX_DEVICES)
+        return hipErrorInvalidDevice;
+    if (!cus[a.device].load())
+    {
+        hipDeviceProp_t prop;
+        const hipError_t e = hipGetDeviceProperties(&prop, a.device);
+        if (e != hipSuccess)
+            return e;
+        cus[a.device].store(prop.multiProcessorCount);
+    }
+    int64_t groups = (int64_t)cus[a.device].load() * 2;
+    if (groups > nblocks)
+        groups = nblocks > 0 ? nblocks : 1;
+    if (a.grid_limit > 0 && groups > a.grid_limit)
+        groups = a.grid_limit;
+    const bool small = !a.full && a.L >= 4;
+    const bool nco = a.nco_word != 0;
+    const int g = (int)groups;
+#define IP_LAUNCH(I16, NCO)                                                                                              \
+    return small ? launch_t<ROWS, I16, NCO, true>(a, nblocks, g) : launch_t<ROWS, I16, NCO, false>(a, nblocks, g)
+    if (a.in_i16)
+    {
+        if (nco)
+            IP_LAUNCH(true, true);
+        IP_LAUNCH(true, false);
+    }
+    if (nco)
+        IP_LAUNCH(false, true);
+    IP_LAUNCH(false, false);
+#undef IP_LAUNCH
+}
+
+template hipError_t launch_interp_fft_rows<IF_FIR_INTERP_ROWS>(const InterpArgs &a);
+
+#endif // IF_FIR_INTERP_ROWS
+
+} // namespace if_fir

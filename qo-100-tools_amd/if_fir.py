@@ -29,11 +29,16 @@ EXPORTS = [
     "if_fir_mc_owner", "if_fir_mc_unique_id", "if_fir_mc_init", "if_fir_mc_destroy", "if_fir_mc_reset",
     "if_fir_mc_set_input_format", "if_fir_mc_process_device", "if_fir_mc_channel_ctx", "if_fir_mc_last_error",
     "if_fir_mc_set_chunk_samples", "if_fir_mc_get_chunk_samples",
+    "if_fir_interp_init", "if_fir_interp_init_complex", "if_fir_interp_destroy", "if_fir_interp_reset", "if_fir_interp_set_backend",
+    "if_fir_interp_get_backend", "if_fir_interp_set_input_format", "if_fir_interp_set_nco", "if_fir_interp_get_nco",
+    "if_fir_interp_set_stream", "if_fir_interp_synchronize", "if_fir_interp_last_error", "if_fir_interp_out_count",
+    "if_fir_interp_process", "if_fir_interp_process_device",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
                "if_fir_debug_bank_plan", "if_fir_debug_bank_tail", "if_fir_debug_fft_schedule",
-               "if_fir_mc_debug_plan", "if_fir_debug_queue_faults"]
+               "if_fir_mc_debug_plan", "if_fir_debug_queue_faults",
+               "if_fir_debug_interp_config", "if_fir_debug_interp_seek", "if_fir_debug_interp_tables"]
 MC_ID_BYTES = 128
 
 
@@ -146,7 +151,41 @@ def _load(path, dev):
     L.if_fir_mc_set_chunk_samples.restype = u8
     L.if_fir_mc_get_chunk_samples.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.if_fir_mc_get_chunk_samples.restype = u8
+    L.if_fir_interp_init.argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u64, i32]
+    L.if_fir_interp_init.restype = u8
+    L.if_fir_interp_init_complex.argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u64, i32]
+    L.if_fir_interp_init_complex.restype = u8
+    L.if_fir_interp_destroy.argtypes = [vp]
+    L.if_fir_interp_destroy.restype = None
+    for name in ("reset", "synchronize"):
+        getattr(L, "if_fir_interp_" + name).argtypes = [vp]
+        getattr(L, "if_fir_interp_" + name).restype = u8
+    for name in ("set_backend", "set_input_format"):
+        getattr(L, "if_fir_interp_" + name).argtypes = [vp, u32]
+        getattr(L, "if_fir_interp_" + name).restype = u8
+    L.if_fir_interp_get_backend.argtypes = [vp]
+    L.if_fir_interp_get_backend.restype = u32
+    L.if_fir_interp_set_nco.argtypes = [vp, ctypes.c_double]
+    L.if_fir_interp_set_nco.restype = u8
+    L.if_fir_interp_get_nco.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+    L.if_fir_interp_get_nco.restype = u8
+    L.if_fir_interp_set_stream.argtypes = [vp, vp]
+    L.if_fir_interp_set_stream.restype = u8
+    L.if_fir_interp_last_error.argtypes = [vp]
+    L.if_fir_interp_last_error.restype = ctypes.c_char_p
+    L.if_fir_interp_out_count.argtypes = [vp, u64]
+    L.if_fir_interp_out_count.restype = u64
+    L.if_fir_interp_process.argtypes = [vp, vp, f32p, u64, ctypes.POINTER(u64)]
+    L.if_fir_interp_process.restype = u8
+    L.if_fir_interp_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.if_fir_interp_process_device.restype = u8
     if dev:
+        L.if_fir_debug_interp_config.argtypes = [vp, u32, u32]
+        L.if_fir_debug_interp_config.restype = u8
+        L.if_fir_debug_interp_seek.argtypes = [vp, u64]
+        L.if_fir_debug_interp_seek.restype = u8
+        L.if_fir_debug_interp_tables.argtypes = [f32p, u32, u32, f32p, u32]
+        L.if_fir_debug_interp_tables.restype = u32
         L.if_fir_time_device.argtypes = [vp, vp, vp, u64, u32, u32, f32p]
         L.if_fir_time_device.restype = u8
         L.if_fir_debug_stamps.argtypes = [vp, ctypes.POINTER(u64), u32]
@@ -391,6 +430,126 @@ class IfFir:
         self._check(self._L.if_fir_dev_download(self._ctx, host.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ptr),
                                               host.nbytes))
         return host
+
+
+class IfFirInterp:
+    """One if_fir_interp_t: upsample by `interpolation`, filter, optionally mix up (docs/SPEC.md §6).  Methods mirror the C
+    entry points; N input samples give N * interpolation outputs."""
+
+    def __init__(self, taps, interpolation, max_samples=1 << 20, device=0, backend=None, complex_taps=False, dev=False):
+        self._L = dev_lib() if dev else lib()
+        taps = np.asarray(taps)
+        if np.iscomplexobj(taps):
+            taps = np.ascontiguousarray(taps.astype(np.complex64)).view(np.float32)
+            complex_taps = True
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        self._ctx = ctypes.c_void_p()
+        self.taps = taps
+        self.interpolation = int(interpolation)
+        self._i16 = False
+        init = self._L.if_fir_interp_init_complex if complex_taps else self._L.if_fir_interp_init
+        if not init(ctypes.byref(self._ctx), _f32p(taps), taps.size // 2 if complex_taps else taps.size, self.interpolation,
+                    int(max_samples), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._L.if_fir_interp_last_error(None).decode())
+        if backend is not None:
+            self.set_backend(backend)
+
+    def _check(self, ok):
+        if not ok:
+            raise IfFirError(self._L.if_fir_interp_last_error(self._ctx).decode())
+
+    def close(self):
+        if self._ctx:
+            self._L.if_fir_interp_destroy(self._ctx)
+            self._ctx = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        self._check(self._L.if_fir_interp_reset(self._ctx))
+
+    def set_backend(self, backend):
+        self._check(self._L.if_fir_interp_set_backend(self._ctx, int(backend)))
+
+    def get_backend(self):
+        return int(self._L.if_fir_interp_get_backend(self._ctx))
+
+    def set_input_format(self, fmt):
+        self._check(self._L.if_fir_interp_set_input_format(self._ctx, int(fmt)))
+        self._i16 = (int(fmt) == INPUT_I16)
+
+    def set_nco(self, freq):
+        """if_fir_interp_set_nco(): mix the OUTPUT up by exp(+j 2 pi f n), n = absolute output index; 0 = off."""
+        self._check(self._L.if_fir_interp_set_nco(self._ctx, float(freq)))
+
+    def get_nco(self):
+        f = ctypes.c_double(0.0)
+        self._check(self._L.if_fir_interp_get_nco(self._ctx, ctypes.byref(f)))
+        return float(f.value)
+
+    def set_stream(self, stream_handle):
+        self._check(self._L.if_fir_interp_set_stream(self._ctx, ctypes.c_void_p(stream_handle or None)))
+
+    def synchronize(self):
+        self._check(self._L.if_fir_interp_synchronize(self._ctx))
+
+    def out_count(self, samples):
+        return int(self._L.if_fir_interp_out_count(self._ctx, int(samples)))
+
+    def process(self, iq):
+        """if_fir_interp_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in,
+        interleaved float32 out."""
+        iq = np.asarray(iq)
+        if self._i16:
+            iq = np.ascontiguousarray(iq, dtype=np.int16).reshape(-1)
+        else:
+            if np.iscomplexobj(iq):
+                iq = np.ascontiguousarray(iq.astype(np.complex64)).view(np.float32)
+            iq = np.ascontiguousarray(iq, dtype=np.float32).reshape(-1)
+        n = iq.size // 2
+        out = np.empty(2 * self.out_count(n), dtype=np.float32)
+        m = ctypes.c_uint64(0)
+        dummy = np.zeros(2, dtype=np.float32)
+        self._check(self._L.if_fir_interp_process(self._ctx, ctypes.c_void_p(iq.ctypes.data if n else dummy.ctypes.data),
+                                                  _f32p(out if out.size else dummy), n, ctypes.byref(m)))
+        assert m.value * 2 == out.size
+        return out
+
+    def process_device(self, dev_in, dev_out, samples):
+        """if_fir_interp_process_device(): raw device pointers (ints), asynchronous.  Returns the output sample count."""
+        m = ctypes.c_uint64(0)
+        self._check(self._L.if_fir_interp_process_device(self._ctx, ctypes.c_void_p(dev_in), ctypes.c_void_p(dev_out),
+                                                         int(samples), ctypes.byref(m)))
+        return int(m.value)
+
+    def debug_config(self, force_full=False, grid_limit=0):
+        """if_fir_debug_interp_config() (development library: construct with dev=True)."""
+        self._check(self._L.if_fir_debug_interp_config(self._ctx, 1 if force_full else 0, int(grid_limit)))
+
+    def debug_seek(self, samples):
+        """if_fir_debug_interp_seek() (development library): the next call's first output index becomes samples * L."""
+        self._check(self._L.if_fir_debug_interp_seek(self._ctx, int(samples)))
+
+
+def debug_interp_tables(taps, complex_taps=False):
+    """if_fir_debug_interp_tables(): the interpolator's multiply table FFT_4096(taps) / 4096 as complex64 (host-only, no GPU)."""
+    taps = np.ascontiguousarray(taps, dtype=np.float32)
+    t = taps.size // 2 if complex_taps else taps.size
+    out = np.zeros(2 * 4096, dtype=np.float32)
+    if dev_lib().if_fir_debug_interp_tables(_f32p(taps), t, 1 if complex_taps else 0, _f32p(out), out.size) != out.size:
+        raise IfFirError("if_fir_debug_interp_tables: %d taps are not served by the overlap-save kernel" % t)
+    return out.view(np.complex64)
 
 
 FFT_TABLE_FLOATS = 2 * (4096 + 4096 + 256 + 1024 + 1024 + 64 + 256)

@@ -579,3 +579,70 @@ def main_odd():
 
 if __name__ == "__main__":
     main_odd()
+
+
+# ---- interpolate-by-L overlap-save (csrc/if_fir_interp.hip) ----------------------------------------------------------
+# One workgroup = one block of 4096 output-rate points held in LDS, transformed by radix-4 (and one radix-2) Stockham passes.
+# Pass (R, Ns) over a sequence of Nf points, j = 0 .. Nf/R - 1, k = j mod Ns:
+#     v[r] = src[j + r Nf/R] * W_{Ns R}^(r k),   V = DFT_R(v),   dst[(j - k) R + k + r Ns] = V[r]
+# Ns runs 1, R1, R1 R2, ...; the result is in natural order (autosort).  A pass reads all its inputs before it writes.
+# The small form (L = 4 s) transforms only the block's 4096/L input samples: the 4096-point transform of the zero-stuffed
+# block is that transform repeated L times, X4096[k] = X_{4096/L}[k mod 4096/L], so the multiply by H reads it modulo 4096/L.
+
+
+def stockham_radices(nf):
+    """The pass radices the kernel runs for an nf-point transform: one radix-2 pass first when log2(nf) is odd, then radix 4."""
+    m = int(nf).bit_length() - 1
+    assert 1 << m == nf
+    return [2] * (m & 1) + [4] * (m // 2)
+
+
+def stockham(x, inverse=False):
+    """The kernel's Stockham transform, pass by pass, with the kernel's twiddle table W4096^i (conjugated for the inverse)."""
+    x = np.asarray(x, dtype=np.complex128).copy()
+    nf = x.size
+    tw = np.exp(-2j * np.pi * np.arange(N) / N)
+    if inverse:
+        tw = tw.conj()
+    ns = 1
+    for R in stockham_radices(nf):
+        nr = nf // R
+        y = np.empty_like(x)
+        for j in range(nr):
+            k = j & (ns - 1)
+            v = np.array([x[j + r * nr] * tw[(r * k * (N // (ns * R))) % N] for r in range(R)])
+            V = np.array([sum(v[q] * (tw[(q * r * (N // R)) % N]) for q in range(R)) for r in range(R)])
+            for r in range(R):
+                y[(j - k) * R + k + r * ns] = V[r]
+        x = y
+        ns *= R
+    return x
+
+
+def interp_block(xin, h, L, small=True):
+    """One overlap-save block of the interpolator: xin = the block's 4096/L input samples; returns the 4096 circular outputs
+    (positions >= T - 1 are the linear convolution of the zero-stuffed block with h).  small: the 4096/L-point forward
+    transform read modulo 4096/L; else the full form's 4096-point transform of the zero-stuffed block."""
+    nf = N // L
+    assert len(xin) == nf
+    Hm = np.fft.fft(np.asarray(h, dtype=np.complex128), N) / N  # the kernel's multiply table (1/4096 folded in)
+    if small:
+        X = stockham(xin)
+        Z = Hm * X[np.arange(N) % nf]
+    else:
+        u = np.zeros(N, dtype=np.complex128)
+        u[::L] = xin
+        Z = Hm * stockham(u)
+    return stockham(Z, inverse=True)
+
+
+def main_interp():
+    rng = np.random.default_rng(11)
+    h = rng.standard_normal(255)
+    for L in (1, 2, 4, 8, 64):
+        xb = rng.standard_normal(N // L) + 1j * rng.standard_normal(N // L)
+        u = np.zeros(N, dtype=np.complex128)
+        u[::L] = xb
+        ref = np.fft.ifft(np.fft.fft(u) * np.fft.fft(h, N))
+        for small in ((False, True) if L >= 4 else (False,)):
+            print("interp block L = %d %s: err %.3g" % (L, "small" if small else "full", np.max(np.abs(interp_block(xb, h, L, small) - ref))))
