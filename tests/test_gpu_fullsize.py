@@ -411,3 +411,260 @@ def test_full_size_filter_bank(fir, oracle, gpu_ok, monkeypatch, d, nch):
         got = outs[c][2 * first_out:2 * first_out + refw.size].cpu().numpy()
         l2, mx = oracle.err_metrics(got, refw)
         assert l2 <= 1e-6 and mx <= 1e-6, (d, s, start, l2, mx)
+
+
+# ---- the filter bank with every channel at its own centre (if_fir_channelizer_process_device_freq, SPEC §3.3) at size --------------
+TOL = 1e-6           # SPEC §3
+MARGIN = 4096        # canary floats on either side of a channel's outputs
+# six centres on the 1/4096 grid, two off it (819/4096 and 0.2 sit on the generator's 0.2 tone, the others see its noise floor)
+BANK_CENTRES = [300 / 4096.0, 819 / 4096.0, -333 / 4096.0, 2047 / 4096.0, -2048 / 4096.0, 1 / 4096.0, 0.2, -0.123456789]
+BANK_MORE = [0.0, 255 / 4096.0, 256 / 4096.0, 257 / 4096.0, 1638 / 4096.0]     # (13 channels: the partial group of four of tail 17)
+
+
+def _on_grid(fc):
+    return fc * 4096.0 == np.round(fc * 4096.0)
+
+
+def _bank_input(torch, f, n, i16):
+    """2^28-class input on the device: the synthetic stream (channel 5); int16: scaled by 12000, rounded and clipped in chunks."""
+    x = torch.empty(2 * n, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    f.synth_device(x.data_ptr(), 0, n, 5)
+    f.synchronize()
+    if not i16:
+        return x
+    xi = torch.empty(2 * n, dtype=torch.int16, device="cuda")
+    step = 1 << 26
+    for a in range(0, 2 * n, step):
+        xi[a:a + step] = torch.clamp(torch.round(x[a:a + step] * 12000.0), -32768, 32767).to(torch.int16)
+    torch.cuda.synchronize()
+    return xi
+
+
+def _samples(xd, i16, lo, hi):
+    """Samples [lo, hi) of the device buffer as the interleaved float32 values the filter sees."""
+    xs = xd[2 * lo:2 * hi].cpu().numpy()
+    return xs.astype(np.float32) * np.float32(2.0 ** -15) if i16 else xs
+
+
+def _window_input(xd, i16, n, t, start, w, continued):
+    """The t - 1 samples before sample `start` of this call and the window's w samples; in front of the call's first sample: zeros, or
+    the end of the same buffer when the call continues a stream of identical buffers."""
+    lo = max(0, start - (t - 1))
+    xs = _samples(xd, i16, lo, start + w)
+    missing = t - 1 - (start - lo)
+    if missing:
+        head = _samples(xd, i16, n - missing, n) if continued else np.zeros(2 * missing, dtype=np.float32)
+        xs = np.concatenate([head, xs])
+    return xs
+
+
+def _bank_outputs(torch, nch, m):
+    """One buffer per channel, MARGIN canary floats on either side of its m outputs."""
+    bufs = [torch.full((2 * m + 2 * MARGIN,), 3.0, dtype=torch.float32, device="cuda") for _ in range(nch)]
+    return bufs, [b[MARGIN:MARGIN + 2 * m] for b in bufs]
+
+
+def _canaries_intact(torch, bufs, m):
+    return all(bool(torch.all(b[:MARGIN] == 3.0)) and bool(torch.all(b[MARGIN + 2 * m:] == 3.0)) for b in bufs)
+
+
+def _max_abs_diff(a, b, step=1 << 27):
+    """(max |a - b|, max |b|) over two device arrays, in slices (no full-size temporaries)."""
+    worst = scale = 0.0
+    for i in range(0, a.numel(), step):
+        worst = max(worst, (a[i:i + step] - b[i:i + step]).abs().max().item())
+        scale = max(scale, b[i:i + step].abs().max().item())
+    return worst, scale
+
+
+def _check_bank_windows(oracle, taps, d, centres, outs, xd, i16, n, consumed, starts, what):
+    """Windows of every channel against tests/bank_ref.py.  starts: (first sample of the window within this call, samples)."""
+    import bank_ref
+    t = len(taps)
+    for start, w in starts:
+        xs = _window_input(xd, i16, n, t, start, w, consumed > 0)
+        first_out = oracle.out_count(consumed, start, d)
+        for c, fc in enumerate(centres):
+            ref = bank_ref.bank_window_ref(oracle, taps, xs, t, d, fc, consumed + start)
+            assert ref.size == 2 * 2048 and np.max(np.abs(ref)) > 0.01
+            got = outs[c][2 * first_out:2 * first_out + ref.size].cpu().numpy()
+            l2, mx = oracle.err_metrics(got, ref)
+            print("%s window d=%d start=%d centre=%.9f: l2=%.3g max=%.3g (largest output %.3g)"
+                  % (what, d, consumed + start, fc, l2, mx, np.max(np.abs(ref))))
+            assert l2 <= TOL and mx <= TOL, (what, d, fc, consumed + start, l2, mx)
+
+
+@pytest.mark.parametrize("d,i16,nch", [(4, False, 8), (4, True, 8), (8, False, 8), (16, False, 8), (16, True, 8), (64, False, 8),
+                                       (12, False, 8), (24, True, 8), (48, False, 8), (16, False, 13), (8, False, 5)])
+def test_full_size_filter_bank_own_centres(fir, oracle, gpu_ok, monkeypatch, d, i16, nch):
+    """The filter bank with every channel at its own centre (if_fir_channelizer_process_device_freq) at the headline size, 2^28 samples
+    = 70 000 blocks through the two-level block queue: each per-channel tail once plain (decimation 4, 8, 16) and once keeping every
+    sub-th output (12; 24; 64 = power of two and 48 = general divisor inside the four-channels-per-inverse tail), float32 and int16,
+    and channel counts that leave a partial group (13 of four, 5 of two).  Per case: the return value, no expired queue wait, canaries on both
+    sides of every channel's buffer; EVERY output of every channel on the 1/4096 grid against a one-channel context with
+    if_fir_set_nco(centre) (both within TOL of the float64 result: 2 TOL of that channel's largest output); windows of 2048 outputs
+    of EVERY channel (first block, first block seam, interior, the last outputs) against the float64 definition (tests/bank_ref.py); one
+    call = two calls at an odd cut, to TOL of the channel's largest output (measured on the MI355X: not bit-identical -- the second call's
+    block grid starts at the cut -- so no equality is asserted).  Measured there over these tests' 448 windows: l2 <= 5.6e-7, max <= 7.0e-7;
+    every output against the one-channel context <= 5.7e-7 of the channel's largest output."""
+    import torch
+    torch.cuda.set_device(0)
+    monkeypatch.setenv("IF_FIR_DEBUG", "1")
+    n, t = 1 << 28, 255
+    taps = fir.bpf_design(t, 0.0, 0.02)
+    centres = {8: BANK_CENTRES, 13: BANK_CENTRES + BANK_MORE, 5: [BANK_CENTRES[i] for i in (0, 1, 4, 6, 7)]}[nch]
+    what = "own_centres[%d-%s-%d]" % (d, "i16" if i16 else "f32", nch)
+    with fir.IfFir(taps, d, 0, dev=True) as f:
+        if i16:
+            f.set_input_format(fir.INPUT_I16)
+        xd = _bank_input(torch, f, n, i16)
+        m = f.out_count(n)
+        assert m == oracle.out_count(0, n, d)
+        bufs, outs = _bank_outputs(torch, nch, m)
+        torch.cuda.synchronize()
+        assert f.get_backend() == fir.BACKEND_HIP_FFT
+        assert f.channelizer_process_device_freq(centres, xd.data_ptr(), [o.data_ptr() for o in outs], n) == m
+        f.synchronize()
+        assert f.debug_queue_faults() == 0
+        assert _canaries_intact(torch, bufs, m)
+        # every output of the channels on the grid: one context that mixes, filters and decimates that channel alone
+        ref = torch.empty(2 * m, dtype=torch.float32, device="cuda")
+        with fir.IfFir(taps, d, 0) as f1:
+            if i16:
+                f1.set_input_format(fir.INPUT_I16)
+            for c, fc in enumerate(centres):
+                if not _on_grid(fc):
+                    continue
+                f1.reset()
+                f1.set_nco(fc)
+                assert f1.process_device(xd.data_ptr(), ref.data_ptr(), n) == m
+                f1.synchronize()
+                worst, scale = _max_abs_diff(outs[c], ref)
+                print("%s every output, centre %.9f: max diff %.3g of largest output %.3g" % (what, fc, worst / scale, scale))
+                assert scale > 0.01 and worst <= 2 * TOL * scale, (what, fc, worst / scale)
+        del ref
+        # windows of every channel against the float64 definition
+        w = 2048 * d
+        seam = 3840 * 5 - 64
+        _check_bank_windows(oracle, taps, d, centres, outs, xd, i16, n, 0,
+                            [(0, w), (seam - seam % d, w), ((n // 3) - (n // 3) % (4 * d), w), ((m - 2048) * d, n - (m - 2048) * d)], what)
+        # one call = two calls at an odd cut (the second call's input in a buffer of its own: aligned, and the cut stays odd for int16)
+        f.reset()
+        cut = (n // 2) + 12345
+        bufs2, part = _bank_outputs(torch, nch, m)
+        torch.cuda.synchronize()
+        m1 = f.channelizer_process_device_freq(centres, xd.data_ptr(), [p.data_ptr() for p in part], cut)
+        tail = xd[2 * cut:].clone()
+        ptail = [torch.empty(2 * (m - m1), dtype=torch.float32, device="cuda") for _ in range(nch)]
+        torch.cuda.synchronize()
+        m2 = f.channelizer_process_device_freq(centres, tail.data_ptr(), [p.data_ptr() for p in ptail], n - cut)
+        f.synchronize()
+        assert m1 == oracle.out_count(0, cut, d) and m1 + m2 == m
+        assert f.debug_queue_faults() == 0
+        same = True
+        for c in range(nch):
+            part[c][2 * m1:] = ptail[c]
+            worst, scale = _max_abs_diff(part[c], outs[c])
+            same = same and torch.equal(part[c], outs[c])
+            assert worst <= TOL * scale, (what, centres[c], worst / scale)
+        print("%s one call vs two calls: bit-identical = %s" % (what, same))
+        assert _canaries_intact(torch, bufs2, m)
+
+
+@pytest.mark.parametrize("d", [4, 8, 16, 48])
+def test_filter_bank_own_centres_past_2_32_samples(fir, oracle, gpu_ok, monkeypatch, d):
+    """A stream continued past 2^32 samples (17 calls of 2^28 samples of one buffer on one context): the only place where the absolute
+    sample index of a bank call no longer fits 32 bits.  The mix-down phase is P a mod 2^32; the centres off the grid have odd P, for
+    which every bit of a below 2^32 counts and a truncated or sign-extended index shows.  (Decimation 48: 2^28 is no multiple of it, so
+    every call also starts at another decimation phase.)  The 17th call's first 2048 outputs of every channel (history = the end of the
+    buffer) and 2048 in its middle against the float64 definition."""
+    import torch
+    torch.cuda.set_device(0)
+    monkeypatch.setenv("IF_FIR_DEBUG", "1")
+    n, t = 1 << 28, 255
+    taps = fir.bpf_design(t, 0.0, 0.02)
+    centres = BANK_CENTRES
+    with fir.IfFir(taps, d, 0, dev=True) as f:
+        xd = _bank_input(torch, f, n, False)
+        mmax = n // d + 1
+        bufs, outs = _bank_outputs(torch, len(centres), mmax)
+        torch.cuda.synchronize()
+        for call in range(17):
+            m = f.channelizer_process_device_freq(centres, xd.data_ptr(), [o.data_ptr() for o in outs], n)
+            assert m == oracle.out_count(call * n, n, d)
+        f.synchronize()
+        assert f.debug_queue_faults() == 0
+        assert _canaries_intact(torch, bufs, mmax)
+        w = 2048 * d
+        _check_bank_windows(oracle, taps, d, centres, outs, xd, False, n, 16 * n, [(0, w), ((n // 2) - (n // 2) % (4 * d) + 4 * d, w)],
+                            "past_2_32[%d]" % d)
+
+
+def test_filter_bank_own_centres_beyond_32_bit_offsets(fir, oracle, gpu_ok, monkeypatch):
+    """One call of 2^31 + 12 293 samples (17 GB of float32 in), three channels at their own centres.  Decimation 4: 4.3 GB per channel,
+    so the per-lane 32-bit store offsets sit on a 64-bit base that passes 2^32 bytes -- windows against the float64 definition at the
+    start, around the 2^32-byte line of the input (sample 2^29) and of the OUTPUT (sample 2^31) and the last 2048 outputs; the channels
+    on the grid whole against a context with if_fir_set_nco; canaries.  Decimation 12 (every 3rd output of the same tail, block indices up to
+    2^31 / 3840 through KeepEvery): the same windows, and every output against every third output of the decimate-by-4 run: the same bits
+    (measured on the MI355X before it was asserted; the single-channel tail has the same property in test_beyond_32_bit_offsets).
+    Peak device memory about 39 GB: 17 in, 3 x 4.3 out, 4.3 for the one-channel reference or 3 x 1.4 for decimation 12."""
+    import torch
+    torch.cuda.set_device(0)
+    monkeypatch.setenv("IF_FIR_DEBUG", "1")
+    t = 255
+    n = (1 << 31) + 12_293
+    taps = fir.bpf_design(t, 0.0, 0.02)
+    centres = [300 / 4096.0, 0.2, -2048 / 4096.0]
+
+    def windows(d, m):
+        w = 2048 * d
+        mids = [(1 << 29) - w // 2, (1 << 31) - w // 2]
+        return [(0, w)] + [(s - s % d, w) for s in mids] + [((m - 2048) * d, n - (m - 2048) * d)]
+
+    with fir.IfFir(taps, 4, 0, dev=True) as f:
+        xd = _bank_input(torch, f, n, False)
+        m = f.out_count(n)
+        assert m == oracle.out_count(0, n, 4) and 8 * m > 1 << 32
+        bufs, outs = _bank_outputs(torch, 3, m)
+        torch.cuda.synchronize()
+        assert f.channelizer_process_device_freq(centres, xd.data_ptr(), [o.data_ptr() for o in outs], n) == m
+        f.synchronize()
+        assert f.debug_queue_faults() == 0
+        assert _canaries_intact(torch, bufs, m)
+        _check_bank_windows(oracle, taps, 4, centres, outs, xd, False, n, 0, windows(4, m), "beyond_32_bit[4]")
+        ref = torch.empty(2 * m, dtype=torch.float32, device="cuda")
+        with fir.IfFir(taps, 4, 0) as f1:
+            for c in (0, 2):
+                f1.reset()
+                f1.set_nco(centres[c])
+                assert f1.process_device(xd.data_ptr(), ref.data_ptr(), n) == m
+                f1.synchronize()
+                worst, scale = _max_abs_diff(outs[c], ref)       # (slices of 2^26 outputs)
+                print("beyond_32_bit[4] every output, centre %.9f: max diff %.3g of largest output %.3g" % (centres[c], worst / scale, scale))
+                assert scale > 0.01 and worst <= 2 * TOL * scale, (centres[c], worst / scale)
+        del ref
+        with fir.IfFir(taps, 12, 0, dev=True) as f12:
+            m12 = f12.out_count(n)
+            assert m12 == oracle.out_count(0, n, 12)
+            bufs12, outs12 = _bank_outputs(torch, 3, m12)
+            torch.cuda.synchronize()
+            assert f12.channelizer_process_device_freq(centres, xd.data_ptr(), [o.data_ptr() for o in outs12], n) == m12
+            f12.synchronize()
+            assert f12.debug_queue_faults() == 0
+            assert _canaries_intact(torch, bufs12, m12)
+            _check_bank_windows(oracle, taps, 12, centres, outs12, xd, False, n, 0, windows(12, m12), "beyond_32_bit[12]")
+            same = True
+            step = 1 << 26
+            for c in range(3):
+                y4, y12 = outs[c].view(-1, 2), outs12[c].view(-1, 2)
+                worst = scale = 0.0
+                for a in range(0, m12, step):
+                    b = min(m12, a + step)
+                    third = y4[3 * a:3 * b:3]
+                    worst = max(worst, (y12[a:b] - third).abs().max().item())
+                    scale = max(scale, third.abs().max().item())
+                    same = same and torch.equal(y12[a:b], third)
+                assert scale > 0.01 and worst <= 2 * TOL * scale, (centres[c], worst / scale)
+            print("beyond_32_bit[12] vs every third decimate-by-4 output: bit-identical = %s" % same)
+            assert same     # (measured on the MI355X: the same tail with two of three stores left out, the same bits)

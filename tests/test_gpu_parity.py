@@ -1059,6 +1059,86 @@ def test_filter_bank_channels_at_arbitrary_centre_frequencies(fir, oracle, torch
             f.channelizer_process_device_freq([0.1], xd.data_ptr(), [xd.data_ptr()], 16)
 
 
+@pytest.mark.parametrize("t,d,i16", [(255, 4, False), (1023, 4, True), (255, 8, False), (511, 8, True), (255, 16, False), (2047, 16, True),
+                                     (255, 12, False), (255, 24, False), (255, 32, True), (255, 48, False), (255, 64, False)])
+def test_filter_bank_own_centres_run_queue_on_small_grid(fir, oracle, torch_cuda, monkeypatch, t, d, i16):
+    """test_fft_backend_run_queue_on_small_grid for the filter bank's per-channel tails (every channel at its own centre): the other
+    bank tests are single-round launches (fewer blocks than the chip has waves), in which the block queue, the runs of blocks per wave and
+    the tail phase never execute.  1 050 007 samples = 270 ... 510 blocks, 13 channels on the 1/4096 grid and 5 off it: the default launch
+    against the float64 reference (the NCO oracle on the grid, the definition of tests/bank_ref.py off it), canaries; at most 1 and 3
+    workgroups (tuning 2000 + k) bit-identical to it, which wave computes a block must not matter; a 120 011-sample call with
+    single-round launches switched off (development tuning 1000000 + 262144) bit-identical to the single-round one; ragged pieces through the
+    one-workgroup grid within tolerance; no expired queue wait."""
+    import bank_ref
+    torch = torch_cuda
+    monkeypatch.setenv("IF_FIR_DEBUG", "1")
+    taps = fir.bpf_design(t, 0.0, 0.02)
+    n, ns = 1_050_007, 120_011
+    if i16:
+        xi = np.clip(np.round(oracle.synth_iq(n, 57) * 12000.0), -32768, 32767).astype(np.int16)
+        x = xi.astype(np.float32) * np.float32(2.0 ** -15)
+        xd = torch.from_numpy(xi).cuda()
+        cuts = [0, 333_333 & ~3, 700_001 & ~3, n]
+    else:
+        x = oracle.synth_iq(n, 57)
+        xd = torch.from_numpy(x).cuda()
+        cuts = [0, 333_333, 700_001, n]
+    on_grid = [b / 4096.0 for b in (0, 1, 255, 256, 257, 300, 819, 2047, -2048, -1, -333, 1638, 77)]       # 13 channels
+    off_grid = [0.2, -0.123456789, 0.05 + 1.0 / 8192 - 1e-9, 0.3333333, 1e-7]
+    x0 = np.concatenate([np.zeros(2 * (t - 1), dtype=np.float32), x])
+
+    def run(f, centres, a, b):
+        """One call on samples [a, b) (a buffer of its own), 8 canary floats behind every channel's outputs."""
+        m_exp = oracle.out_count(a, b - a, d)
+        outs = [torch.full((2 * m_exp + 8,), 3.0, dtype=torch.float32, device="cuda") for _ in centres]
+        piece = xd[2 * a:2 * b].clone()
+        torch.cuda.synchronize()
+        assert f.channelizer_process_device_freq(centres, piece.data_ptr(), [o.data_ptr() for o in outs], b - a) == m_exp
+        f.synchronize()
+        res = [o.cpu().numpy() for o in outs]
+        assert all(np.all(o[2 * m_exp:] == 3.0) for o in res)
+        return [o[:2 * m_exp] for o in res]
+
+    for centres in (on_grid, off_grid):
+        if centres is on_grid:
+            refs = [oracle.fir_nco_f64(taps, x, d, oracle.nco_phase_word(fc)) for fc in centres]
+        else:
+            refs = [bank_ref.bank_window_ref(oracle, taps, x0, t, d, fc, 0) for fc in centres]
+        with fir.IfFir(taps, d, n, dev=True) as f:
+            if i16:
+                f.set_input_format(fir.INPUT_I16)
+            assert f.get_backend() == fir.BACKEND_HIP_FFT
+            y0 = run(f, centres, 0, n)
+            for c, fc in enumerate(centres):
+                l2, mx = oracle.err_metrics(y0[c], refs[c])
+                assert l2 <= TOL and mx <= TOL, (t, d, i16, fc, l2, mx)
+            for k in (1, 3):
+                f.reset()
+                f.set_tuning(2000 + k)
+                yk = run(f, centres, 0, n)
+                for c, fc in enumerate(centres):
+                    assert np.array_equal(yk[c], y0[c]), (k, fc, int(np.argmax(yk[c] != y0[c])))
+            # a single-round call, and the same call through the queue
+            f.set_tuning(0)
+            f.reset()
+            ys = run(f, centres, 0, ns)
+            f.reset()
+            f.set_tuning(1262144)
+            yq = run(f, centres, 0, ns)
+            for c, fc in enumerate(centres):
+                assert np.array_equal(yq[c], ys[c]), (fc, int(np.argmax(yq[c] != ys[c])))
+                l2, mx = oracle.err_metrics(ys[c], refs[c][:ys[c].size])
+                assert l2 <= TOL and mx <= TOL, (t, d, i16, fc, l2, mx)
+            # ragged pieces through the one-workgroup grid: the first block of a call takes the history path
+            f.reset()
+            f.set_tuning(2001)
+            parts = [run(f, centres, a, b) for a, b in zip(cuts[:-1], cuts[1:])]
+            for c, fc in enumerate(centres):
+                l2, mx = oracle.err_metrics(np.concatenate([p[c] for p in parts]), refs[c])
+                assert l2 <= TOL and mx <= TOL, (t, d, i16, fc, l2, mx)
+            assert f.debug_queue_faults() == 0
+
+
 def test_random_configurations_against_the_oracle(fir, oracle):
     """Sweep of random (taps, decimation, length, backend, piece cuts, input format, NCO) combinations: every result
     within SPEC tolerance of the float64 oracle, the bit-exact kernels equal to their order models."""
@@ -1120,8 +1200,9 @@ def test_random_filter_bank_configurations_against_the_oracle(fir, oracle, torch
     rng = np.random.default_rng(int(os.environ.get("IF_FIR_TEST_SEED", "20261004")) + 17)   # other seeds: soak runs
     schedule = [("slots", 4), ("slots", 8), ("slots", 16), ("freq", 4), ("freq", 8), ("freq", 16), ("nco", 8), ("nco", 16), ("allslots", 8),
                 ("freq", 12), ("freq", 24), ("freq", 32), ("freq", 64), ("freq", 40),
-                ("slots", 32), ("slots", 12), ("nco", 24), ("nco", 64)]   # every form in turn, the rest random
-    for case in range(54):
+                ("slots", 32), ("slots", 12), ("nco", 24), ("nco", 64),
+                ("freq", 48), ("freq", 20), ("freq", 56)]   # every form in turn, three times each
+    for case in range(63):
         kind, d = schedule[case % len(schedule)]
         t = int(rng.choice([1, 2, 17, 63, 64, 65, 127, 255, 256, 257, 511, 777, 1023, 1025, 2047, 3073]))
         n = int(rng.integers(1, 40_000))

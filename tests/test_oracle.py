@@ -226,3 +226,27 @@ def test_nco_oracle_matches_golden_and_identity(oracle, gold):
         assert np.array_equal(np.concatenate([y1, y2]), y)
     # phase word 0 = no NCO
     assert np.array_equal(oracle.fir_nco_f64(h, x, 4, 0), oracle.fir_f64(h, x, 4))
+
+
+@pytest.mark.parametrize("d", [4, 12, 16, 64])
+@pytest.mark.parametrize("centre", [300 / 4096.0, -0.5])
+def test_bank_window_reference_equals_the_nco_oracle_past_2_32_samples(oracle, d, centre):
+    """tests/bank_ref.py (the by-definition float64 form of a filter-bank channel on a window of a long stream, SPEC §3.3)
+    against the C oracle: for a centre on the 1/4096 grid the two are the same numbers.  The window starts past 2^32
+    samples, where the mix-down phase needs the 64-bit sample index; 2048 outputs, history from the stream."""
+    import bank_ref
+    t = 255
+    taps = oracle.bpf_design(t, 0.0, 0.02)
+    start = (1 << 32) + 1000 * d
+    w = 2048 * d
+    xs = oracle.synth_iq(t - 1 + w, 5, start - (t - 1))
+    got = bank_ref.bank_window_ref(oracle, taps, xs, t, d, centre, start)
+    ref = oracle.fir_nco_f64(taps, xs[2 * (t - 1):], d, oracle.nco_phase_word(centre), hist=xs[:2 * (t - 1)], consumed=start)
+    assert got.shape == ref.shape == (2 * 2048,)
+    assert np.max(np.abs(ref)) > 1e-3
+    assert np.allclose(got, ref, rtol=0.0, atol=1e-12 * np.max(np.abs(ref)))
+    # the stream's first samples: zeros in front of sample 0
+    x0 = oracle.synth_iq(w, 5, 0)
+    got0 = bank_ref.bank_window_ref(oracle, taps, np.concatenate([np.zeros(2 * (t - 1), np.float32), x0]), t, d, centre, 0)
+    ref0 = oracle.fir_nco_f64(taps, x0, d, oracle.nco_phase_word(centre))
+    assert np.allclose(got0, ref0, rtol=0.0, atol=1e-12 * np.max(np.abs(ref0)))
