@@ -86,6 +86,11 @@ uint8_t if_fir_debug_interp_seek(if_fir_interp_t *pCtx, uint64_t ullSamples);
 /* host-only: the interpolator's multiply table H[k] = FFT_4096(taps)[k] / 4096 as 4096 (re, im) pairs (ulOutFloats >= 8192);
  * returns the floats written, 0 when the taps are not served by the overlap-save kernel */
 uint32_t if_fir_debug_interp_tables(const float *pfTaps, uint32_t ulTaps, uint32_t bComplexTaps, float *pfOut, uint32_t ulOutFloats);
+/* host-only: what the interpolator decides for (taps, interpolation): *pulRows = the overlap-save kernel's overlap in rows of 64
+ * outputs (the unit launched; 48 beyond its range), *pulHistLen = input samples of history kept between calls, *pbFftOk = 1 when
+ * the overlap-save backend serves the pair; 0 = taps or interpolation outside if_fir_interp_init's range */
+uint8_t if_fir_debug_interp_plan(uint32_t ulTaps, uint32_t ulInterpolation, uint32_t *pulRows, uint32_t *pulHistLen,
+                                 uint32_t *pbFftOk);
 
 #ifdef __cplusplus
 }

@@ -428,4 +428,16 @@ IF_FIR_API uint32_t if_fir_debug_interp_tables(const float *pfTaps, uint32_t ulT
     memcpy(pfOut, H.data(), H.size() * sizeof(float2));
     return 2u * if_fir::INTERP_N;
 }
+
+IF_FIR_API uint8_t if_fir_debug_interp_plan(uint32_t ulTaps, uint32_t ulInterpolation, uint32_t *pulRows, uint32_t *pulHistLen,
+                                            uint32_t *pbFftOk)
+{
+    if (!pulRows || !pulHistLen || !pbFftOk || ulTaps == 0 || ulTaps > IF_FIR_MAX_TAPS || ulInterpolation < 1 ||
+        ulInterpolation > IF_FIR_MAX_INTERPOLATION)
+        return 0;
+    *pulRows = (uint32_t)if_fir::interp_overlap_rows((int)ulTaps);
+    *pulHistLen = (uint32_t)if_fir::interp_hist_len((int)ulTaps, (int)ulInterpolation);
+    *pbFftOk = if_fir::interp_fft_supported((int)ulTaps, (int)ulInterpolation) ? 1u : 0u;
+    return 1;
+}
 #endif

@@ -38,7 +38,7 @@ EXPORTS = [
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
                "if_fir_debug_bank_plan", "if_fir_debug_bank_tail", "if_fir_debug_fft_schedule",
                "if_fir_mc_debug_plan", "if_fir_debug_queue_faults",
-               "if_fir_debug_interp_config", "if_fir_debug_interp_seek", "if_fir_debug_interp_tables"]
+               "if_fir_debug_interp_config", "if_fir_debug_interp_seek", "if_fir_debug_interp_tables", "if_fir_debug_interp_plan"]
 MC_ID_BYTES = 128
 
 
@@ -186,6 +186,8 @@ def _load(path, dev):
         L.if_fir_debug_interp_seek.restype = u8
         L.if_fir_debug_interp_tables.argtypes = [f32p, u32, u32, f32p, u32]
         L.if_fir_debug_interp_tables.restype = u32
+        L.if_fir_debug_interp_plan.argtypes = [u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]
+        L.if_fir_debug_interp_plan.restype = u8
         L.if_fir_time_device.argtypes = [vp, vp, vp, u64, u32, u32, f32p]
         L.if_fir_time_device.restype = u8
         L.if_fir_debug_stamps.argtypes = [vp, ctypes.POINTER(u64), u32]
@@ -550,6 +552,16 @@ def debug_interp_tables(taps, complex_taps=False):
     if dev_lib().if_fir_debug_interp_tables(_f32p(taps), t, 1 if complex_taps else 0, _f32p(out), out.size) != out.size:
         raise IfFirError("if_fir_debug_interp_tables: %d taps are not served by the overlap-save kernel" % t)
     return out.view(np.complex64)
+
+
+def debug_interp_plan(taps, interpolation):
+    """if_fir_debug_interp_plan(): (overlap rows, history length in input samples, overlap-save backend serves the pair) for a
+    tap count and an interpolation (host-only, no GPU)."""
+    rows, hist, ok = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+    if not dev_lib().if_fir_debug_interp_plan(int(taps), int(interpolation), ctypes.byref(rows), ctypes.byref(hist), ctypes.byref(ok)):
+        raise IfFirError("if_fir_debug_interp_plan: %d taps, interpolation %d are outside if_fir_interp_init's range"
+                         % (int(taps), int(interpolation)))
+    return int(rows.value), int(hist.value), bool(ok.value)
 
 
 FFT_TABLE_FLOATS = 2 * (4096 + 4096 + 256 + 1024 + 1024 + 64 + 256)
