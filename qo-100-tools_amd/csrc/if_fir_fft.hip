@@ -18,7 +18,7 @@
 // kernel, its launcher and the explicit instantiation of launch_fft_rows<ROWS>; the 32-row unit also carries the two-partition
 // launches), once more per overlap length with -DIF_FIR_FFT_DEC2_UNIT on top (the decimate-by-2 tails' instantiations,
 // round 5), once with -DIF_FIR_FFT_ODD (the odd-decimation kernel) and once with none of them (host side:
-// tables, routing predicates, launch_fft) -- so that the instantiations compile in parallel.
+// tables, launch_fft) -- so that the instantiations compile in parallel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -30,7 +30,7 @@
 #include "if_fir_kernels.h"
 #include "if_fir_fft_queue.h"
 
-// the host side (tables, routing predicates, launch_fft) is the unit compiled without a kernel selector
+// the host side (tables, launch_fft) is the unit compiled without a kernel selector
 #if !defined(IF_FIR_FFT_ROWS) && !defined(IF_FIR_FFT_ODD)
 #define IF_FIR_FFT_HOST 1
 #endif
@@ -48,19 +48,19 @@ namespace if_fir
 #if defined(IF_FIR_FFT_HAZARD_PROBE) && !defined(IF_FIR_FFT_DEC2_UNIT)
 #define IF_FIR_FFT_DEC2_UNIT 1 // (the probe instantiates the decimate-by-2 tail)
 #endif
-// (round 5: the decimate-by-2 tails, CHAN 2 and 3, are instantiated in units of their own, -DIF_FIR_FFT_DEC2_UNIT: more units to compile in
+// (round 5: the decimate-by-2 tails, TAIL_DEC2 and TAIL_DEC2_SUB, are instantiated in units of their own, -DIF_FIR_FFT_DEC2_UNIT: more units to compile in
 // parallel, and per-family build flags for tools/build_ab.sh)
 #include "if_fir_fft_kernel.inc"
 template <int ROWS>
-hipError_t launch_fft_rows(const LaunchArgs &a); // defined and explicitly instantiated in the unit compiled with IF_FIR_FFT_ROWS = ROWS
-hipError_t launch_fft_two_partitions(const LaunchArgs &a); // (in the 32-row unit)
+hipError_t launch_fft_rows(const LaunchArgs &a, const FftRoute &r); // defined and explicitly instantiated in the unit compiled with IF_FIR_FFT_ROWS = ROWS
+hipError_t launch_fft_two_partitions(const LaunchArgs &a, const FftRoute &r); // (in the 32-row unit)
 #include "if_fir_fft_launch.inc"
 #endif // IF_FIR_FFT_ROWS
 
 #ifdef IF_FIR_FFT_HOST // ================= host side =================
 template <int ROWS>
-hipError_t launch_fft_rows(const LaunchArgs &a); // defined and explicitly instantiated in the unit compiled with IF_FIR_FFT_ROWS = ROWS
-hipError_t launch_fft_two_partitions(const LaunchArgs &a); // (in the 32-row unit)
+hipError_t launch_fft_rows(const LaunchArgs &a, const FftRoute &r); // defined and explicitly instantiated in the unit compiled with IF_FIR_FFT_ROWS = ROWS
+hipError_t launch_fft_two_partitions(const LaunchArgs &a, const FftRoute &r); // (in the 32-row unit)
 #include "if_fir_fft_host.inc"
 #endif // host side
 

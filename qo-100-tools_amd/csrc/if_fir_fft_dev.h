@@ -305,8 +305,6 @@ __device__ __forceinline__ constexpr int phys(int i, int j)
     return 4 * (i + 4 * (j & 1) + 8 * ((j >> 1) & 1)) + (j >> 2);
 }
 
-constexpr int FFT_N = 4096;
-constexpr int FFT_PART = 2048; // filters of 3074..4096 taps: two partitions of at most this many taps
 constexpr int XROW = 136;             // bytes per 16-entry row of the exchange buffers (16*8 + 8 pad)
 constexpr int XREG = 16 * XROW + 32;  // one 16x16 region (+32 so that the 4 regions start on different banks)
 constexpr int XBUF = 4 * XREG;        // per-wave exchange buffer
@@ -349,14 +347,16 @@ __device__ __forceinline__ cf lds_phasor(const f2v *pht, uint32_t ph) // exp(+j 
 // 2^28-sample launches lose 2-3 % with more cached rows; configs[1] (2^26 samples) GAINS 4.5 % at 16 rows each side -- half of its
 // 512 MB input, i.e. the 256 MB memory-side cache serving the same bytes again on the benchmark's next launch: an artefact of
 // re-filtering one buffer, not a property of a stream in service, so it was not adopted.
-// Kernel argument of the tails: the filter-bank forms (CHAN >= 4) take the whole ChanArgs (2.4 KB by value), the single-channel
+// Kernel argument of the tails: the filter-bank forms (tail_is_bank) take the whole ChanArgs (2.4 KB by value), the single-channel
 // kernels only the thinning factor -- the headline path's launches then copy 150 bytes of kernel arguments instead of 2.5 KB
 struct ChanNone
 {
     uint32_t sub;
 };
+// (tail_is_bank(CHAN) as the literal comparison: the expression is part of every kernel's mangled name, which tests, profile tools and resource files match)
 template <int CHAN>
 using chan_arg_t = typename std::conditional<(CHAN >= 4), ChanArgs, ChanNone>::type;
+static_assert(tail_is_bank(4) && !tail_is_bank(3), "chan_arg_t's condition is tail_is_bank");
 constexpr int LDS_Q = LDS_XB + FFT_WAVES * XBUF; // workgroup block queue: slot counter (16 B) + ring of group entries
 constexpr int LDS_QPTR = LDS_Q + 16 + Q_RING * 8; // 16-slot bank: the 16 output pointers (kept out of the SGPRs)
 constexpr int LDS_QNCO = LDS_QPTR + 16 * 8; // bank tails with an NCO: the block's rotation phasor, one 8-byte word per wave
@@ -537,7 +537,7 @@ constexpr int FFT_LOAD_AUX = 2, FFT_STORE_AUX = 2;
 // block's stores (the cold load path drains its loads before it joins the steady-state path, if_fir_fft_kernel.inc) the fourth
 // batch's extra lead is worth 0.1-0.5 % (profiles/r05_table_prefetch_ab.txt): 4.
 constexpr int FFT_EARLY_GROUPS = 4;
-// (the tail that keeps every sub-th output, CHAN 1 = decimation 8, 12, ..., 64, computes 15 store offsets on top: with four early batches and
+// (the tail that keeps every sub-th output, TAIL_DEC4_SUB = decimation 8, 12, ..., 64, computes 15 store offsets on top: with four early batches and
 // unpaired LDS reads two of its instantiations' cold paths needed 4 VGPRs of scratch; three batches there)
 constexpr int FFT_EARLY_GROUPS_SUB = 3;
 // (round 5, profiles/r05_lds_single_reads.txt) LDS reads as single ds_read_b64: the compiler's machine-level load/store optimizer pairs the

@@ -1,139 +1,23 @@
 // if_fir_fft_host.inc -- part of the overlap-save kernel's source (if_fir_fft.hip includes it; not a translation unit of its own).
-// Host side (the unit compiled without a kernel selector): routing predicates, launch_fft, the table images.
-// D = 1 and D = 4 have their own kernels; any other decimation runs the full-rate kernel with a selecting store.
-// Taps: the first T-1 outputs of a 4096-point block are discarded, in whole 64-sample rows (4, 8, 16, 32 or 48 of the
-// 64): up to 257 taps cost 6 % of the block, 513 taps 12.5 %, 1025 taps 25 %, 2049 taps half, 3073 taps three quarters.
-// Routing of a decimation-8 filter-bank call whose channels sit on the slot grid (launch_fft_rows; one definition for the launcher and
-// the CPU test): a slot parity with at least four channels, none of the call's slots listed twice, is served by ONE all-slots launch
-// (pmask[parity] = its slots, else 0); `rest` = bit c set for every channel c left to the per-channel form.
-void fft_bank8_plan(const uint32_t *slots, uint32_t count, bool all_slots_available, uint32_t pmask[2], uint32_t *rest)
-{
-    uint32_t seen = 0, m[2] = {0, 0};
-    int npar[2] = {0, 0};
-    bool dup = false;
-    for (uint32_t c = 0; c < count; c++)
-    {
-        const uint32_t sl = slots[c] & 15u;
-        dup = dup || ((seen >> sl) & 1u);
-        seen |= 1u << sl;
-        m[sl & 1u] |= 1u << sl;
-        npar[sl & 1u]++;
-    }
-    *rest = 0;
-    for (int par = 0; par < 2; par++)
-        pmask[par] = (all_slots_available && !dup && npar[par] >= 4) ? m[par] : 0u;
-    for (uint32_t c = 0; c < count; c++)
-        if (!((pmask[slots[c] & 1u] >> (slots[c] & 15u)) & 1u))
-            *rest |= 1u << c;
-}
-
-// The filter bank's tail for a decimation: 4, 8, 16 themselves; channels at their own centres (`general`) also every other multiple
-// of 4 up to 64 -- the largest of 16, 8, 4 that divides it, the tail then keeps every (D / F)-th output.  0: not served.
-int fft_bank_tail(int D, bool general)
-{
-    if (D == 4 || D == 8 || D == 16)
-        return D;
-    if (!general || D < 4 || D > 64 || (D & 3))
-        return 0;
-    return (D % 16 == 0) ? 16 : (D % 8 == 0) ? 8 : 4;
-}
-
-bool fft_supported(int T, int D)
-{
-    return D >= 1 && D <= 64 && T >= 1 && T <= 4096;
-}
-
-// Which decimations have a decimating tail (frequency-domain alias fold + small inverse): every EVEN one, D = F * sub with F the
-// tail's own decimation.  F = 4: decimation 4 and every other multiple of 4 up to 64 -- the decimate-by-4 tail keeping every
-// sub-th output (round 3; measured faster than the one-channel filter-bank tails at 8 / 16 it replaced for single channels,
-// profiles/r03_composite_decimations.txt).  F = 2: decimation 2, and 6, 10, ..., 62 the same way behind the decimate-by-2 tail.
-// Odd decimations run the full-rate kernel with a selecting store.  Filters of 3074..4096 taps (two partitions) take the same
-// tails, the second partition accumulating.  One definition for the launcher, the shim's tables and the multi-channel
-// front's chunk grid.
-bool fft_tail(int T, int D, int *pF, int *pSub)
-{
-    int F = 1;
-    if (D >= 1 && D <= 64 && T >= 1 && T <= 4096)
-        F = (D % 4 == 0) ? 4 : (D % 2 == 0) ? 2 : 1;
-    if (pF)
-        *pF = F;
-    if (pSub)
-        *pSub = D / F;
-    return F > 1;
-}
-
-// 3074..4096 taps: two partitions of at most FFT_PART taps each, y = h_a * x + h_b * (x delayed by FFT_PART)
-bool fft_two_partitions(int T)
-{
-    return T > 3073;
-}
-
-// Odd decimations divisible by 3 or 5 (round 4, fir_odd_kernel): D = F sub; a block of F x 1024 input samples gives 1024 outputs
-// at the fs/F rate, the first ceil((T - 1 + F - 1) / F) of which are invalid -- dropped as 2, 4 or 8 rows of 64.
-bool fft_odd_tail(int T, int D, int *pF, int *pSub, int *pOvlr)
-{
-    int F = 1, ovlr = 0;
-    if (D >= 3 && D <= 64 && (D & 1) && T >= 1 && !fft_two_partitions(T))
-    {
-        // (F = 5 -- decimation 5, 25, 35, 55 -- was written and dropped: five phase streams of 16 registers + the transforms'
-        // temporaries do not fit 256 VGPRs, the compiler spilled 112 of them; those decimations keep the selecting store)
-        F = (D % 3 == 0) ? 3 : 1;
-        if (F > 1)
-        {
-            const int need = (T - 1 + F - 1 + F - 1) / F; // outputs of a block that see samples ahead of it
-            // (8 dropped rows -- up to 1535 taps -- were built and measured 18 % slower than the selecting store: half of every
-            // block is overlap, profiles/r04_odd_decimation.txt)
-            ovlr = need <= 128 ? 2 : need <= 256 ? 4 : 0;
-            if (!ovlr)
-                F = 1;
-        }
-    }
-    if (pF)
-        *pF = F;
-    if (pSub)
-        *pSub = F > 1 ? D / F : 1;
-    if (pOvlr)
-        *pOvlr = ovlr;
-    return F > 1;
-}
-
-// Overlap rows of the (taps, decimation) pair.  (Round 4 built and measured a 2-row kernel, L = 3968, for filters of at most 129
-// taps on the full-rate pipeline -- 16 913 instead of 17 477 blocks for BASELINE configs[1]: within 1 % of the 4-row kernel on a
-// stream that is not re-read from the memory-side cache, profiles/r04_two_row_overlap.txt -- and removed it again.)
-int fft_overlap_rows(int T, int D)
-{
-    if (fft_two_partitions(T))
-        return 32; // each partition runs the 32-row kernel
-    (void)D;
-    return (T - 1 <= 256) ? 4 : (T - 1 <= 512) ? 8 : (T - 1 <= 1024) ? 16 : (T - 1 <= 2048) ? 32 : 48;
-}
-
-// new input samples per block of the overlap-save kernel for this filter: streams cut at multiples of it (and of the
-// decimation) give bit-identical results to the unsplit stream (the multi-channel front's chunk unit)
-int fft_block_advance(int T, int D)
-{
-    int F = 1, ovlr = 0;
-    if (fft_odd_tail(T, D, &F, nullptr, &ovlr))
-        return F * (1024 - 64 * ovlr);
-    return fft_two_partitions(T) ? FFT_N - FFT_PART : FFT_N - 64 * fft_overlap_rows(T, D);
-}
-
+// Host side (the unit compiled without a kernel selector): launch_fft, the table images (routing: if_fir_fft_route.h).
 hipError_t launch_fft(const LaunchArgs &a)
 {
-    if (!fft_supported(a.T, a.D) || !a.fft_tables)
+    if (!a.fft_tables)
         return hipErrorInvalidConfiguration;
-    if (!a.chan && !a.no_fold && fft_odd_tail(a.T, a.D, nullptr, nullptr, nullptr))
+    const FftRoute r = fft_route_of(a);
+    if (r.family == FFT_FAMILY_ODD)
         return launch_fft_odd(a);
-    if (fft_two_partitions(a.T))
-        return launch_fft_two_partitions(a);
-    const int rows = fft_overlap_rows(a.T, a.D);
-    switch (rows)
+    if (r.family == FFT_FAMILY_TWO_PARTITIONS)
+        return launch_fft_two_partitions(a, r);
+    if (r.family != FFT_FAMILY_ROWS) // (the call is not served)
+        return hipErrorInvalidConfiguration;
+    switch (r.rows)
     {
-    case 4: return launch_fft_rows<4>(a);
-    case 8: return launch_fft_rows<8>(a);
-    case 16: return launch_fft_rows<16>(a);
-    case 32: return launch_fft_rows<32>(a);
-    default: return launch_fft_rows<48>(a);
+    case 4: return launch_fft_rows<4>(a, r);
+    case 8: return launch_fft_rows<8>(a, r);
+    case 16: return launch_fft_rows<16>(a, r);
+    case 32: return launch_fft_rows<32>(a, r);
+    default: return launch_fft_rows<48>(a, r);
     }
 }
 
@@ -223,9 +107,11 @@ void fft_phasor_tables(float *tables)
 //   [32 KB, 64 KB)  hp [(i*16+k2)*64 + lane]   = FFT(taps)[(4*(lane/16)+i) + 16*(lane%16) + 256*k2] / 4096
 //   [64 KB, 66 KB)  tw2[k1*16 + n2]            = W256^(n2*k1)
 //   [66 KB, 82 KB)  twd, twe: twiddles of the decimate-by-4 1024-point inverse
-void fft_build_tables(const float *taps, int T, int ctaps, int D, uint32_t nco_delta, double in_scale,
-                      float *tables /* FFT_TABLE_FLOATS floats */, int bank, int full_rate, int bank_parity)
+void fft_build_tables(const float *taps, int T, int ctaps, const FftImage &image, uint32_t nco_delta, double in_scale,
+                      float *tables /* FFT_TABLE_FLOATS floats */)
 {
+    const int bank = image.kind == FFT_IMAGE_BANK8 ? 8 : image.kind == FFT_IMAGE_BANK16 ? 16 : 0, bank_parity = image.parity;
+    const int D = image.kind == FFT_IMAGE_DEC4 ? 4 : 1, full_rate = image.kind == FFT_IMAGE_FULL_RATE;
     const double PI2 = 6.283185307179586476925286766559;
     float *tw1 = tables, *hp = tables + 2 * 4096, *tw2 = tables + 4 * 4096;
     float *twd = tw2 + 2 * 256, *twe = twd + 2 * 1024, *ncob = twe + 2 * 1024, *twf = ncob + 2 * 64;
@@ -313,7 +199,7 @@ void fft_build_tables(const float *taps, int T, int ctaps, int D, uint32_t nco_d
     if (bank == 8)
     {
         // filter bank at decimation 8: G_q[a] = W16^(a q) sum_j H(k0 + 16 k1 + 256 (q + 2 j)) W8^(a j) at ((i*16 + 8 q + a)*64 + lane)
-        // (second stage of pass 3, the multiplication by the slot's H and the 8-way alias fold merged; kernel, CHAN == 8)
+        // (second stage of pass 3, the multiplication by the slot's H and the 8-way alias fold merged; kernel, TAIL_BANK8_CHANNEL)
         for (int i = 0; i < 4; i++)
             for (int lane = 0; lane < 64; lane++)
                 for (int q = 0; q < 2; q++)
@@ -329,7 +215,7 @@ void fft_build_tables(const float *taps, int T, int ctaps, int D, uint32_t nco_d
                         }
                         // Round 4: the bank's forward passes are the decimate-by-4 kernels' ((cos, tan) twiddles on the inputs of passes 2
                         // and 3), so the factor b^a, b = W4096^(k0 + 16 k1), that input a of pass 3 still carries is folded in here.
-                        // This image serves the per-channel forms (CHAN == 8) and the all-slots form's even slots (CHAN == 9);
+                        // This image serves the per-channel forms (TAIL_BANK8_CHANNEL) and the all-slots form's even slots (TAIL_BANK8_ALL);
                         // bank_parity = 1: the all-slots form's image for the ODD slots -- also the slot twiddle's common factor W16^a,
                         // and the halves exchanged (first half: the factor of w0 = G_1, second: G_0)
                         int half = q;
@@ -353,7 +239,7 @@ void fft_build_tables(const float *taps, int T, int ctaps, int D, uint32_t nco_d
     if (bank == 16)
     {
         // 16-slot filter bank at the channel rate: G0[n2] = sum_k2 H(k0 + 16 k1 + 256 k2) W16^(n2 k2) at ((i*16 + n2)*64 + lane)
-        // (pass 3, the multiplication by the slot's H and the 16-way alias fold merged; see the kernel, CHAN == 16)
+        // (pass 3, the multiplication by the slot's H and the 16-way alias fold merged; see the kernel, TAIL_BANK16_ALL)
         for (int i = 0; i < 4; i++)
             for (int lane = 0; lane < 64; lane++)
                 for (int n2 = 0; n2 < 16; n2++)

@@ -1,15 +1,6 @@
 // if_fir_fft_kernel.inc -- part of the overlap-save kernel's source (if_fir_fft.hip includes it; not a translation unit of its own).
 // fir_fft_kernel: load, forward transform, block queue; the tails of a block live in if_fir_fft_tails_bank.inc / _single.inc.
-// The tail of a block after the forward transform, by CHAN (DEC4 = any decimating tail; DESIGN.md §3.4, §3.4.1, §3.7):
-//    0  full rate (DEC4 = false; DECN: selecting store), or the decimate-by-4 tail       1  decimate-by-4 tail keeping every sub-th output
-//    2  decimate-by-2 tail                                                                3  the same keeping every sub-th output
-//    4  filter bank at decimation 4, channels on the fs/16 slot grid (per channel)        5  the same, every channel at its own centre bin
-//    6  tail 5 keeping every sub-th output (decimation 12, 20, 28, ...; tails 8-general and 17 do that inside, by a wave-uniform branch)
-//    8  filter bank at decimation 8 per channel: slot grid (NCO = false) / any centre bin or a common offset (NCO = true)
-//    9  filter bank at decimation 8, all slots of one parity from two 8-point transforms per group
-//   16  filter bank at decimation 16, all 16 slots from one 16-point transform per group (NCO: a common offset)
-//   17  filter bank at decimation 16 per channel, every channel at its own centre bin
-// (round 5: compiled with single LDS reads, IF_FIR_LDS_SINGLE_READS in if_fir_fft_dev.h)
+// CHAN names the tail of a block after the forward transform: the TAIL_* constants and their traits, if_fir_fft_route.h.
 template <int OVL_ROWS, bool DEC4, bool I16, bool NCO, int CHAN, bool DECN, bool ACC>
 __global__ __launch_bounds__(512, 2) IF_FIR_LDS_SINGLE_READS void fir_fft_kernel(const f2v *__restrict__ in_, f2v *__restrict__ out,
                                                         const f2v *__restrict__ tables, const f2v *__restrict__ hist,
@@ -21,35 +12,27 @@ __global__ __launch_bounds__(512, 2) IF_FIR_LDS_SINGLE_READS void fir_fft_kernel
 {
     // ACC (filters of 3074..4096 taps, two partitions of <= 2048 taps): this launch filters the input DELAYED by in_shift
     // samples with the second partition's table and adds its result to what the first launch stored
-    // (round 3: also behind the single-channel decimating tails, CHAN 0..3, so that two-partition filters decimate in the
+    // (round 3: also behind the single-channel decimating tails (tail_single), so that two-partition filters decimate in the
     // frequency domain like shorter ones)
-    static_assert(!ACC || (CHAN <= 3 && OVL_ROWS == 32), "accumulating store: single-channel pipelines, 32 overlap rows");
-    static_assert(!DECN || (!DEC4 && !CHAN), "general decimation = the full-rate pipeline with a selecting store");
-    // CHAN names the decimating tail beyond the plain decimate-by-4 one: 2 = single channel, decimation 2 (frequency-domain
-    // fold + 2048-point inverse); 4 / 8 / 16 = the filter bank at that decimation
-    // (1 = the decimate-by-4 tail keeping every sub-th output: decimation 8, 12, ..., 64; 3 = the decimate-by-2 tail doing the same:
-    // decimation 6, 10, ..., 62)
-    // (9, round 4 = the bank at decimation 8 in its all-slots form: the eight slots of ONE parity from two 8-point transforms per group)
-    static_assert(CHAN == 0 || ((CHAN == 1 || CHAN == 2 || CHAN == 3 || CHAN == 4 || CHAN == 5 || CHAN == 6 || CHAN == 8 || CHAN == 9 || CHAN == 16 || CHAN == 17) && DEC4),
-                  "decimating tails: 1, 2, 3, or the bank at 4 (4: slots, 5: any centre), 8 (8: per channel, 9: all slots of a parity), 16 (16: all slots, 17: per channel)");
-    static_assert((CHAN != 5 && CHAN != 6) || !NCO, "channels at their own centres: no common offset on top");
-    static_assert(CHAN != 17 || !NCO, "channels at their own centres: no common offset on top");
-    static_assert(CHAN != 4 || !NCO, "the decimate-by-4 bank takes no NCO (a single channel with an NCO is the DEC4 kernel)");
+    static_assert(!ACC || (tail_single(CHAN) && OVL_ROWS == 32), "accumulating store: single-channel pipelines, 32 overlap rows");
+    static_assert(!DECN || (!DEC4 && CHAN == TAIL_FULL_OR_DEC4), "general decimation = the full-rate pipeline with a selecting store");
+    static_assert(tail_valid(CHAN) && (CHAN == TAIL_FULL_OR_DEC4 || DEC4), "every named tail but the first is a decimating one");
+    static_assert(tail_has_nco(CHAN) || !NCO, "channels at their own centres: no common offset on top; the decimate-by-4 bank takes no NCO either");
     // 2 overlap rows (<= 129 taps, round 4): the full-rate pipeline only -- the decimating tails drop whole 64-output rows of the
     // fs/F-rate block (OVL_ROWS / 4, / 2, ...), which 128 samples are not
     static_assert(OVL_ROWS >= 4 || (!DEC4 && !ACC), "2 overlap rows: full-rate pipeline (D = 1, odd D) only");
     // diag (development only, results are wrong when set): 1 = skip the global loads, 2 = skip the global stores
     // decimate-by-4 kernels (single channel incl. the multiples of 4, and the bank at decimation 4): twiddles in (cos, tan) form
     // on the inputs of passes 2 and 3 and of the small inverse (round 4); every other tail keeps round 3's form and tables
-    constexpr bool TAN = DEC4 && (CHAN == 0 || CHAN == 1 || CHAN == 4 || CHAN == 5 || CHAN == 6 || CHAN == 8 || CHAN == 9 || CHAN == 16 || CHAN == 17); // (8, 9, 16, 17: the banks' own images)
+    constexpr bool TAN = tail_wants_tan(CHAN, DEC4);
     // the full-rate pipeline the same way, forward and inverse (the inverse's twiddles already sat on the inputs of its passes)
     constexpr bool TANF = !DEC4;
     constexpr int OVL = 64 * OVL_ROWS;
     constexpr int ISZ = I16 ? 4 : 8;       // bytes per input sample
     const char *in = reinterpret_cast<const char *>(in_);
     constexpr int L = FFT_N - OVL;         // new input samples per block
-    constexpr int LOUT = (CHAN == 16 || CHAN == 17) ? L / 16 : (CHAN == 8 || CHAN == 9) ? L / 8 : (CHAN == 2 || CHAN == 3) ? L / 2 : DEC4 ? L / 4 : L; // outputs per block (per channel)
-    constexpr int EARLY_GROUPS = CHAN == 1 ? FFT_EARLY_GROUPS_SUB : FFT_EARLY_GROUPS; // dec4: batches of next-block loads issued during pass 3
+    constexpr int LOUT = tail_lout(CHAN, DEC4, L); // outputs per block (per channel)
+    constexpr int EARLY_GROUPS = CHAN == TAIL_DEC4_SUB ? FFT_EARLY_GROUPS_SUB : FFT_EARLY_GROUPS; // dec4: batches of next-block loads issued during pass 3
     constexpr int LAUX = FFT_LOAD_AUX; // cache policy of the row loads
     constexpr int EDGE = OVL_ROWS; // first / last rows of a block loaded with the default policy
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -65,10 +48,10 @@ __global__ __launch_bounds__(512, 2) IF_FIR_LDS_SINGLE_READS void fir_fft_kernel
         return;
     }
     cf r[64];
-    // CHAN 9 with both slot parities in ONE launch (chan.sub bit 1; round 4): the queue hands out VIRTUAL blocks 2 b + parity -- block b of
+    // TAIL_BANK8_ALL with both slot parities in ONE launch (chan.sub bit 1; round 4): the queue hands out VIRTUAL blocks 2 b + parity -- block b of
     // the stream is transformed twice, by neighbouring waves of a workgroup, and the second read of its rows is served by L2
-    const bool both = (CHAN == 9) && ((chan.sub & 2u) != 0u);
-    auto rb = [&](int64_t b) -> int64_t { return (CHAN == 9 && both) ? (b >> 1) : b; }; // virtual block -> block of the stream
+    const bool both = (CHAN == TAIL_BANK8_ALL) && ((chan.sub & 2u) != 0u);
+    auto rb = [&](int64_t b) -> int64_t { return (CHAN == TAIL_BANK8_ALL && both) ? (b >> 1) : b; }; // virtual block -> block of the stream
     bool loaded = false; // the rows of `blk` are already in flight (issued by the prologue or the previous iteration's epilogue)
     // ---- first block: static (wave w of workgroup b takes block w of global group b), and its rows are requested BEFORE
     //      the table copy below, so that the two transfers overlap at the head of the launch
@@ -113,12 +96,12 @@ __global__ __launch_bounds__(512, 2) IF_FIR_LDS_SINGLE_READS void fir_fft_kernel
         for (int k = 0; k < NK; k++)
             if ((int)threadIdx.x + 512 * k < NV)
                 dst[threadIdx.x + 512 * k] = tv[k];
-        if constexpr (CHAN == 16 || CHAN == 9)
+        if constexpr (CHAN == TAIL_BANK16_ALL || CHAN == TAIL_BANK8_ALL)
         {
             if (threadIdx.x < 16)
                 reinterpret_cast<float2 **>(smem + LDS_QPTR)[threadIdx.x] = chan.out[threadIdx.x];
         }
-        if constexpr (CHAN == 8 || CHAN == 17 || CHAN == 5 || CHAN == 6)
+        if constexpr (CHAN == TAIL_BANK8_CHANNEL || tail_own_centres(CHAN))
         {
             // per channel, the phasors of output rows 0..15 of a block: row k is 32 outputs (decimation 16: 16, decimation 4: 64) = 256
             // input samples behind row 0
@@ -346,14 +329,14 @@ __global__ __launch_bounds__(512, 2) IF_FIR_LDS_SINGLE_READS void fir_fft_kernel
         const srd_t osrd = make_srd(out + obase, (diag & 2) ? 0 : (M - obase) * 8);
         // filter-bank tails with an NCO: the block's share of the output rotation, phasor(phi0 + delta obase), wave-uniform;
         // parked in a per-wave LDS word until the tails need it (the 16-slot tail has neither SGPRs nor VGPRs to spare)
-        if constexpr (NCO && (CHAN == 16 || CHAN == 9))
+        if constexpr (NCO && (CHAN == TAIL_BANK16_ALL || CHAN == TAIL_BANK8_ALL))
         {
             const float2 pb = phasor(nco_phi0 + nco_delta * (uint32_t)obase);
             if (lane == 0)
                 *reinterpret_cast<cf *>(smem + LDS_QNCO + wid * 8) = (cf){pb.x, pb.y};
         }
         // ---- the tail of the block, by family (textual includes: one kernel body, the families in their own files) ----
-        if constexpr (CHAN >= 4)
+        if constexpr (tail_is_bank(CHAN))
         {
 #include "if_fir_fft_tails_bank.inc"
         }

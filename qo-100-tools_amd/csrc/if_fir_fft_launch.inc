@@ -1,26 +1,25 @@
 // if_fir_fft_launch.inc -- part of the overlap-save kernel's source (if_fir_fft.hip includes it; not a translation unit of its own).
-// Launchers of the per-overlap-length units: launch_fft_t, launch_fft_rows (routing of a call to its instantiation), the two-partition launches.
-// the kernel of an instantiation; the decimate-by-2 tails (CHAN 2, 3) are instantiated in units of their own (-DIF_FIR_FFT_DEC2_UNIT, csrc/Makefile)
+// Launchers of the per-overlap-length units: launch_fft_t, launch_fft_form (the (int16, NCO) dispatch), launch_fft_rows (a route's instantiation), the two-partition launches.
+// the kernel of an instantiation; the decimate-by-2 tails (tail_in_dec2_units) are instantiated in units of their own (-DIF_FIR_FFT_DEC2_UNIT, csrc/Makefile)
 template <int OVL_ROWS, bool DEC4, bool I16, bool NCO, int CHAN, bool DECN, bool ACC>
 static constexpr auto fft_kernel_of()
 {
 #ifdef IF_FIR_FFT_DEC2_UNIT
-    static_assert(CHAN == 2 || CHAN == 3, "the decimate-by-2 units hold the decimate-by-2 tails only");
+    static_assert(tail_in_dec2_units(CHAN), "the decimate-by-2 units hold the decimate-by-2 tails only");
 #else
-    static_assert(CHAN != 2 && CHAN != 3, "the decimate-by-2 tails live in the decimate-by-2 units (launch_fft_dec2_rows)");
+    static_assert(!tail_in_dec2_units(CHAN), "the decimate-by-2 tails live in the decimate-by-2 units (launch_fft_dec2_rows)");
 #endif
     return &fir_fft_kernel<OVL_ROWS, DEC4, I16, NCO, CHAN, DECN, ACC>;
 }
-// the decimate-by-2 units' entry point: chan = 2 (decimation 2) | 3 (decimation 6, 10, ..., 62), key = (int16 input ? 2 : 0) | (NCO ? 1 : 0),
-// acc = the second launch of a two-partition filter (32 overlap rows only)
+// the decimate-by-2 units' entry point (tail = TAIL_DEC2 | TAIL_DEC2_SUB); acc = the second launch of a two-partition filter (32 overlap rows only)
 template <int ROWS>
-hipError_t launch_fft_dec2_rows(const LaunchArgs &a, int chan, int key, bool acc);
-template <int OVL_ROWS, bool DEC4, bool I16, bool NCO, int CHAN = 0, bool DECN = false, bool ACC = false>
+hipError_t launch_fft_dec2_rows(const LaunchArgs &a, int tail, bool nco, bool acc);
+template <int OVL_ROWS, bool DEC4, bool I16, bool NCO, int CHAN, bool DECN, bool ACC>
 static hipError_t launch_fft_t(const LaunchArgs &a)
 {
     auto kern = fft_kernel_of<OVL_ROWS, DEC4, I16, NCO, CHAN, DECN, ACC>();
     constexpr int L = FFT_N - 64 * OVL_ROWS;
-    constexpr int LOUT = (CHAN == 16 || CHAN == 17) ? L / 16 : (CHAN == 8 || CHAN == 9) ? L / 8 : (CHAN == 2 || CHAN == 3) ? L / 2 : DEC4 ? L / 4 : L;
+    constexpr int LOUT = tail_lout(CHAN, DEC4, L);
     static DeviceSetup setup;
     int ncus = 0;
     {
@@ -30,21 +29,21 @@ static hipError_t launch_fft_t(const LaunchArgs &a)
     }
     // DECN: the kernel runs at full rate over the N inputs (blocks, run queue, history as for D = 1) and keeps every
     // D-th output, the first one at full-rate index n0
-    // (decimation 4 sub behind the decimate-by-4 tail, CHAN == 1: the tail runs at the fs/4 rate and keeps every sub-th output)
-    constexpr int F = (CHAN == 16 || CHAN == 17) ? 16 : (CHAN == 8 || CHAN == 9) ? 8 : (CHAN == 2 || CHAN == 3) ? 2 : DEC4 ? 4 : 1; // the tail's own decimation
+    // (a thinning tail, e.g. decimation 4 sub behind TAIL_DEC4_SUB: the tail runs at the fs/F rate and keeps every sub-th output)
+    constexpr int F = tail_factor(CHAN, DEC4); // the tail's own decimation
     ChanArgs ca = a.chan ? *a.chan : ChanArgs{};
-    ca.sub = (CHAN == 1 || CHAN == 5 || CHAN == 6) ? (uint32_t)(a.D / 4) : CHAN == 3 ? (uint32_t)(a.D / 2) : CHAN == 9 ? (ca.sub & 3u) /* bit 0: the parity, bit 1: both parities */
-             : (CHAN == 8 && NCO) ? (uint32_t)(a.D / 8) : CHAN == 17 ? (uint32_t)(a.D / 16) : 1u; // (general bank forms: D = F x sub)
-    const int64_t m_rate = DECN ? a.N : CHAN == 9 ? a.M : (a.M - 1) * (int64_t)ca.sub + 1; // (CHAN 9: `sub` carries the slot parity)
+    ca.sub = tail_sub_word(CHAN, DEC4, a.D, ca.sub);
+    const bool both = CHAN == TAIL_BANK8_ALL && (ca.sub & 2u); // both slot parities in one launch: virtual blocks
+    const int64_t m_rate = DECN ? a.N : CHAN == TAIL_BANK8_ALL ? a.M : (a.M - 1) * (int64_t)ca.sub + 1; // (tail 9: `sub` carries the slot parity)
     const int32_t n0_rate = DECN ? 0 : a.n0;
-    const int64_t nblocks = (a.M > 0 ? (m_rate + LOUT - 1) / LOUT : 0) * ((CHAN == 9 && (ca.sub & 2u)) ? 2 : 1); // (both parities: virtual blocks)
+    const int64_t nblocks = (a.M > 0 ? (m_rate + LOUT - 1) / LOUT : 0) * (both ? 2 : 1);
     if (nblocks <= 0)
         return hipSuccess;
     const int64_t wgs_max = (a.grid_limit > 0 && a.grid_limit < ncus) ? a.grid_limit : ncus;
     // (round 5) a call of at most one block per wave of the chip is a SINGLE-ROUND launch (fft_launch_plan; the kernel's bit 131072).  Not for the
     // all-slots bank launch over virtual blocks (the two parities of a block want neighbouring waves: the second read of its rows comes from L2) and
     // not under the development switch 262144.  Diag 256 (development) switches the queue's tail phase off.
-    const FftLaunchPlan plan = fft_launch_plan(nblocks, wgs_max, !(CHAN == 9 && (ca.sub & 2u)) && !(a.diag & 262144),
+    const FftLaunchPlan plan = fft_launch_plan(nblocks, wgs_max, !both && !(a.diag & 262144),
                                                (a.diag & 256) ? 0 : Q_TAIL_MAX_ROUNDS);
     uint32_t qsel = 0;
     {
@@ -53,7 +52,7 @@ static hipError_t launch_fft_t(const LaunchArgs &a)
             return e;
     }
     chan_arg_t<CHAN> cak;
-    if constexpr (CHAN >= 4)
+    if constexpr (tail_is_bank(CHAN))
         cak = ca;
     else
         cak.sub = ca.sub;
@@ -69,224 +68,166 @@ static hipError_t launch_fft_t(const LaunchArgs &a)
     return fft_queue_launched(a);
 }
 
+// THE (int16 input, NCO) dispatch: the two runtime booleans of a call become template arguments here and nowhere else.  FORMS states
+// which NCO instantiations the call site can reach: both (by `nco`), never (tails without any: tail_has_nco) or always.
+// (The units' objects list their kernels in the order of instantiation -- the order of the cases here and of the calls below.)
+enum { NCO_NEVER, NCO_BOTH, NCO_ALWAYS };
+template <int ROWS, bool DEC4, int CHAN, bool DECN = false, bool ACC = false, int FORMS = tail_has_nco(CHAN) ? NCO_BOTH : NCO_NEVER>
+static hipError_t launch_fft_form(const LaunchArgs &a, bool nco = false)
+{
+    static_assert(FORMS == NCO_NEVER || tail_has_nco(CHAN), "this tail has no NCO instantiation");
+    if constexpr (FORMS == NCO_BOTH)
+        switch ((a.in_i16 ? 2 : 0) | (nco ? 1 : 0))
+        {
+        case 0: return launch_fft_t<ROWS, DEC4, false, false, CHAN, DECN, ACC>(a);
+        case 1: return launch_fft_t<ROWS, DEC4, false, true, CHAN, DECN, ACC>(a);
+        case 2: return launch_fft_t<ROWS, DEC4, true, false, CHAN, DECN, ACC>(a);
+        default: return launch_fft_t<ROWS, DEC4, true, true, CHAN, DECN, ACC>(a);
+        }
+    else
+        return a.in_i16 ? launch_fft_t<ROWS, DEC4, true, FORMS == NCO_ALWAYS, CHAN, DECN, ACC>(a)
+                        : launch_fft_t<ROWS, DEC4, false, FORMS == NCO_ALWAYS, CHAN, DECN, ACC>(a);
+}
+
 #ifdef IF_FIR_FFT_DEC2_UNIT
 template <int ROWS>
-hipError_t launch_fft_dec2_rows(const LaunchArgs &a, int chan, int key, bool acc)
+hipError_t launch_fft_dec2_rows(const LaunchArgs &a, int tail, bool nco, bool acc)
 {
-    if constexpr (ROWS >= 4)
-    {
-#define IF_FIR_DEC2_SWITCH(CHAN, ACC)                                                    \
-    switch (key)                                                                       \
-    {                                                                                  \
-    case 0: return launch_fft_t<ROWS, true, false, false, CHAN, false, ACC>(a);        \
-    case 1: return launch_fft_t<ROWS, true, false, true, CHAN, false, ACC>(a);         \
-    case 2: return launch_fft_t<ROWS, true, true, false, CHAN, false, ACC>(a);         \
-    default: return launch_fft_t<ROWS, true, true, true, CHAN, false, ACC>(a);         \
-    }
-        if constexpr (ROWS == 32)
-            if (acc)
-            {
-                if (chan == 2)
-                    IF_FIR_DEC2_SWITCH(2, true)
-                IF_FIR_DEC2_SWITCH(3, true)
-            }
+    const bool plain = tail == TAIL_DEC2;
+    if constexpr (ROWS == 32)
         if (acc)
-            return hipErrorInvalidConfiguration;
-        if (chan == 2)
-            IF_FIR_DEC2_SWITCH(2, false)
-        IF_FIR_DEC2_SWITCH(3, false)
-#undef IF_FIR_DEC2_SWITCH
-    }
-    return hipErrorInvalidConfiguration;
+            return plain ? launch_fft_form<ROWS, true, TAIL_DEC2, false, true>(a, nco) : launch_fft_form<ROWS, true, TAIL_DEC2_SUB, false, true>(a, nco);
+    if (acc)
+        return hipErrorInvalidConfiguration;
+    return plain ? launch_fft_form<ROWS, true, TAIL_DEC2>(a, nco) : launch_fft_form<ROWS, true, TAIL_DEC2_SUB>(a, nco);
 }
 #if defined(IF_FIR_FFT_ONLY) // (development: ONE instantiation of this unit's kernel)
 __attribute__((used)) static auto *const if_fir_fft_only_kernel = &fir_fft_kernel<IF_FIR_FFT_ONLY>;
 #elif defined(IF_FIR_FFT_HAZARD_PROBE) // (tests/test_host.py: one instantiation, the decimate-by-2 tail with its 16-byte stores)
-template __global__ void fir_fft_kernel<IF_FIR_FFT_ROWS, true, false, false, 2, false, false>(
+template __global__ void fir_fft_kernel<IF_FIR_FFT_ROWS, true, false, false, TAIL_DEC2, false, false>(
     const f2v *, f2v *, const f2v *, const f2v *, int, int64_t, int32_t, int64_t, int64_t, int64_t, unsigned int *,
-    unsigned long long *, int32_t, uint32_t, uint32_t, chan_arg_t<2>, uint32_t, void *, int32_t, int32_t, int64_t, int32_t);
+    unsigned long long *, int32_t, uint32_t, uint32_t, chan_arg_t<TAIL_DEC2>, uint32_t, void *, int32_t, int32_t, int64_t, int32_t);
 #else
-template hipError_t launch_fft_dec2_rows<IF_FIR_FFT_ROWS>(const LaunchArgs &a, int chan, int key, bool acc);
+template hipError_t launch_fft_dec2_rows<IF_FIR_FFT_ROWS>(const LaunchArgs &a, int tail, bool nco, bool acc);
 #endif
 #else // ================= the units of every other tail =================
+// the filter bank at decimation 8 (and behind 24, 40, 56: r.sub > 1), per channel (pairs share a small inverse) or all slots of a parity
 template <int ROWS>
-static hipError_t launch_all_slots(const LaunchArgs &p, bool nco) // the decimation-8 bank's all-slots form (tail 9)
+static hipError_t launch_fft_bank8(const LaunchArgs &a, const FftRoute &r)
 {
-    if constexpr (ROWS >= 4)
-        switch ((p.in_i16 ? 2 : 0) | (nco ? 1 : 0))
-        {
-        case 0: return launch_fft_t<ROWS, true, false, false, 9>(p);
-        case 1: return launch_fft_t<ROWS, true, false, true, 9>(p);
-        case 2: return launch_fft_t<ROWS, true, true, false, 9>(p);
-        default: return launch_fft_t<ROWS, true, true, true, 9>(p);
-        }
-    return hipErrorInvalidConfiguration;
-}
-template <int ROWS>
-hipError_t launch_fft_rows(const LaunchArgs &a)
-{
-    int F = 1;
-    const bool tail = fft_tail(a.T, a.D, &F, nullptr);
-    const int key = (a.in_i16 ? 2 : 0) | (a.nco_word ? 1 : 0);
-    if constexpr (ROWS >= 4)
+    // slot form (chan->tw[] = W16^(a slot), a = 1..7) when every channel sits on the fs/16 grid and the context has no NCO;
+    // the general form (chan->bin[] / pword[]: centre bin and mix-down word of a channel) otherwise
+    bool general = a.chan->general || r.sub != 1;
+    for (uint32_t c = 0; c < a.chan->count; c++)
+        general = general || (a.chan->bin[c] & 255u) || a.chan->pword[c] != (a.chan->bin[c] << 20) + a.nco_word;
+    if (general)
+        return launch_fft_form<ROWS, true, TAIL_BANK8_CHANNEL, false, false, NCO_ALWAYS>(a);
+    const bool nco = a.nco_word != 0; // channels on the slot grid shifted by the context's NCO (a common offset)
+    // Channels on the slot grid.  A parity (even / odd slots) with at least four channels, none listed twice, runs the
+    // ALL-SLOTS form (round 4): one launch computes the eight slots of that parity from two 8-point transforms per group
+    // (2340 packed instructions a block whatever the count, against 1008 + 415 per channel) and stores the wanted ones; the
+    // other channels keep the per-channel form.  Both parities qualifying: ONE launch over virtual blocks (kernel).  Up to two
+    // launches per call on the context's stream; only the first one writes the next call's history.
+    const ChanArgs &cin = *a.chan;
+    uint32_t pmask[2], rest = 0;
+    // (diag 4096, development: per-channel form only)
+    fft_bank8_plan(cin.slot, cin.count, a.fft_tables_b != nullptr && !(a.diag & 4096), pmask, &rest);
+    bool first = true;
+    // one all-slots launch for the slots of `mask`; sub = the slot parity, or 2: both parities over virtual blocks
+    const auto all_slots = [&](uint32_t mask, uint32_t sub, const void *tables) -> hipError_t {
+        ChanArgs cs{};
+        cs.count = (uint32_t)__builtin_popcount(mask);
+        cs.sub = sub;
+        cs.rot_e = cin.abs0n0 & 15u;
+        cs.abs0n0 = cin.abs0n0;
+        cs.mask16 = mask;
+        for (uint32_t c = 0; c < cin.count; c++)
+            if ((mask >> (cin.slot[c] & 15u)) & 1u)
+                cs.out[cin.slot[c] & 15u] = cin.out[c];
+        LaunchArgs p = a;
+        p.chan = &cs;
+        p.fft_tables = tables;
+        if (!first)
+            p.hist_out = nullptr;
+        first = false;
+        return launch_fft_form<ROWS, true, TAIL_BANK8_ALL>(p, nco);
+    };
+    if (pmask[0] && pmask[1] && !(a.diag & 8192)) // both parities: ONE launch over virtual blocks (diag 8192, development: two launches)
     {
+        const hipError_t e = all_slots(pmask[0] | pmask[1], 2u, a.fft_tables);
+        if (e != hipSuccess)
+            return e;
+        pmask[0] = pmask[1] = 0;
+    }
+    for (uint32_t par = 0; par < 2; par++)
+        if (pmask[par]) // (even slots: the bank's own image; odd slots: the image behind it)
+        {
+            const hipError_t e = all_slots(pmask[par], par, par ? a.fft_tables_b : a.fft_tables);
+            if (e != hipSuccess)
+                return e;
+        }
+    ChanArgs cl{};
+    for (uint32_t c = 0; c < cin.count; c++)
+    {
+        if (!((rest >> c) & 1u))
+            continue;
+        const uint32_t k = cl.count++;
+        cl.slot[k] = cin.slot[c];
+        for (int w = 0; w < 30; w++)
+            cl.tw[k][w] = cin.tw[c][w];
+        cl.rot0[k][0] = cin.rot0[c][0];
+        cl.rot0[k][1] = cin.rot0[c][1];
+        cl.out[k] = cin.out[c];
+        cl.bin[k] = cin.bin[c];
+        cl.pword[k] = cin.pword[c];
+    }
+    cl.abs0n0 = cin.abs0n0;
+    if (!cl.count)
+        return hipSuccess;
+    LaunchArgs p = a;
+    p.chan = &cl;
+    if (!first)
+        p.hist_out = nullptr;
+    if (nco) // (the slot form proper has no NCO: the left-over channels of a shifted grid take the general form)
+        return launch_fft_form<ROWS, true, TAIL_BANK8_CHANNEL, false, false, NCO_ALWAYS>(p);
+    return launch_fft_form<ROWS, true, TAIL_BANK8_CHANNEL, false, false, NCO_NEVER>(p);
+}
+
+template <int ROWS>
+hipError_t launch_fft_rows(const LaunchArgs &a, const FftRoute &r)
+{
     if (a.chan)
     {
         // the filter bank: decimation 4, 8, 16; channels at their own centres (chan->general) also at every other multiple of 4 up to 64,
         // behind the tail of the largest of 16, 8, 4 that divides the decimation, keeping every sub-th output
-        const int Fb = fft_bank_tail(a.D, a.chan->general != 0);
-        if (!Fb || a.chan->count < 1 || a.chan->count > CHAN_MAX || (Fb == 4 && a.nco_word))
+        if (a.chan->count < 1 || a.chan->count > CHAN_MAX)
             return hipErrorInvalidConfiguration;
-        const int ckey = (a.in_i16 ? 2 : 0) | (a.nco_word ? 1 : 0);
-        if (Fb == 8) // per channel (pairs share a small inverse)
+        switch (r.tail)
         {
-            // slot form (chan->tw[] = W16^(a slot), a = 1..7) when every channel sits on the fs/16 grid and the context has no NCO;
-            // the general form (chan->bin[] / pword[]: centre bin and mix-down word of a channel) otherwise
-            bool general = a.chan->general || a.D != 8;
-            for (uint32_t c = 0; c < a.chan->count; c++)
-                general = general || (a.chan->bin[c] & 255u) || a.chan->pword[c] != (a.chan->bin[c] << 20) + a.nco_word;
-            if (general)
-                return a.in_i16 ? launch_fft_t<ROWS, true, true, true, 8>(a) : launch_fft_t<ROWS, true, false, true, 8>(a);
-            const bool nco = a.nco_word != 0; // channels on the slot grid shifted by the context's NCO (a common offset)
-            // Channels on the slot grid.  A parity (even / odd slots) with at least four channels, none listed twice, runs the
-            // ALL-SLOTS form (round 4): one launch computes the eight slots of that parity from two 8-point transforms per group
-            // (2340 packed instructions a block whatever the count, against 1008 + 415 per channel) and stores the wanted ones; the
-            // other channels keep the per-channel form.  Both parities qualifying: ONE launch over virtual blocks (kernel).  Up to two
-            // launches per call on the context's stream; only the first
-            // one writes the next call's history.  (Even slots: the bank's own table image; odd slots: fft_tables_b.)
-            const ChanArgs &cin = *a.chan;
-            uint32_t pmask[2], rest = 0;
-            // (diag 4096, development: per-channel form only)
-            fft_bank8_plan(cin.slot, cin.count, a.fft_tables_b != nullptr && !(a.diag & 4096), pmask, &rest);
-            bool first = true;
-            if (pmask[0] && pmask[1] && !(a.diag & 8192)) // both parities: ONE launch over virtual blocks (diag 8192, development: two launches)
-            {
-                ChanArgs cs{};
-                cs.count = (uint32_t)__builtin_popcount(pmask[0] | pmask[1]);
-                cs.sub = 2u;
-                cs.rot_e = cin.abs0n0 & 15u;
-                cs.abs0n0 = cin.abs0n0;
-                cs.mask16 = pmask[0] | pmask[1];
-                for (uint32_t c = 0; c < cin.count; c++)
-                    if ((cs.mask16 >> (cin.slot[c] & 15u)) & 1u)
-                        cs.out[cin.slot[c] & 15u] = cin.out[c];
-                LaunchArgs p = a;
-                p.chan = &cs;
-                const hipError_t e = launch_all_slots<ROWS>(p, nco);
-                if (e != hipSuccess)
-                    return e;
-                first = false;
-                pmask[0] = pmask[1] = 0;
-            }
-            for (uint32_t par = 0; par < 2; par++)
-            {
-                if (!pmask[par])
-                    continue;
-                ChanArgs cs{};
-                cs.count = (uint32_t)__builtin_popcount(pmask[par]);
-                cs.sub = par;
-                cs.rot_e = cin.abs0n0 & 15u;
-                cs.abs0n0 = cin.abs0n0;
-                cs.mask16 = pmask[par];
-                for (uint32_t c = 0; c < cin.count; c++)
-                    if ((pmask[par] >> (cin.slot[c] & 15u)) & 1u)
-                        cs.out[cin.slot[c] & 15u] = cin.out[c];
-                LaunchArgs p = a;
-                p.chan = &cs;
-                p.fft_tables = par ? a.fft_tables_b : a.fft_tables; // (even slots: the bank's own image; odd slots: the image behind it)
-                if (!first)
-                    p.hist_out = nullptr;
-                const hipError_t e = launch_all_slots<ROWS>(p, nco);
-                if (e != hipSuccess)
-                    return e;
-                first = false;
-            }
-            ChanArgs cl{};
-            for (uint32_t c = 0; c < cin.count; c++)
-            {
-                if (!((rest >> c) & 1u))
-                    continue;
-                const uint32_t k = cl.count++;
-                cl.slot[k] = cin.slot[c];
-                for (int w = 0; w < 30; w++)
-                    cl.tw[k][w] = cin.tw[c][w];
-                cl.rot0[k][0] = cin.rot0[c][0];
-                cl.rot0[k][1] = cin.rot0[c][1];
-                cl.out[k] = cin.out[c];
-                cl.bin[k] = cin.bin[c];
-                cl.pword[k] = cin.pword[c];
-            }
-            cl.abs0n0 = cin.abs0n0;
-            if (!cl.count)
-                return hipSuccess;
-            LaunchArgs p = a;
-            p.chan = &cl;
-            if (!first)
-                p.hist_out = nullptr;
-            if (nco) // (the slot form proper has no NCO: the left-over channels of a shifted grid take the general form)
-                return a.in_i16 ? launch_fft_t<ROWS, true, true, true, 8>(p) : launch_fft_t<ROWS, true, false, true, 8>(p);
-            return a.in_i16 ? launch_fft_t<ROWS, true, true, false, 8>(p) : launch_fft_t<ROWS, true, false, false, 8>(p);
-        }
-        if (Fb == 16 && a.chan->general) // every channel at its own centre (per channel; arrays indexed by channel)
-            return a.in_i16 ? launch_fft_t<ROWS, true, true, false, 17>(a) : launch_fft_t<ROWS, true, false, false, 17>(a);
-        if (Fb == 16) // all 16 slots from one forward transform; chan->out[] / rot0[] are indexed by SLOT
-            switch (ckey)
-            {
-            case 0: return launch_fft_t<ROWS, true, false, false, 16>(a);
-            case 1: return launch_fft_t<ROWS, true, false, true, 16>(a);
-            case 2: return launch_fft_t<ROWS, true, true, false, 16>(a);
-            default: return launch_fft_t<ROWS, true, true, true, 16>(a);
-            }
-        if (a.chan->general && a.D == 4) // decimation 4, every channel at its own centre
-            return a.in_i16 ? launch_fft_t<ROWS, true, true, false, 5>(a) : launch_fft_t<ROWS, true, false, false, 5>(a);
-        if (a.chan->general) // decimation 12, 20, 28, ...: the same tail keeping every (D / 4)-th output
-            return a.in_i16 ? launch_fft_t<ROWS, true, true, false, 6>(a) : launch_fft_t<ROWS, true, false, false, 6>(a);
-        return a.in_i16 ? launch_fft_t<ROWS, true, true, false, 4>(a) : launch_fft_t<ROWS, true, false, false, 4>(a);
-    }
-    if (a.D == 2 && !a.no_fold) // frequency-domain fold + 2048-point inverse (round 3)
-        return launch_fft_dec2_rows<ROWS>(a, 2, key, false);
-    if (a.D == 4)
-        switch (key)
-        {
-        case 0: return launch_fft_t<ROWS, true, false, false>(a);
-        case 1: return launch_fft_t<ROWS, true, false, true>(a);
-        case 2: return launch_fft_t<ROWS, true, true, false>(a);
-        default: return launch_fft_t<ROWS, true, true, true>(a);
-        }
-    if (tail && F == 2 && !a.no_fold) // decimation 6, 10, ..., 62: the decimate-by-2 tail keeping every sub-th output
-        return launch_fft_dec2_rows<ROWS>(a, 3, key, false);
-    if (tail && F == 4) // decimation 8, 12, ..., 64: the decimate-by-4 tail keeping every sub-th output (tables as for decimation 4)
-        switch (key)
-        {
-        case 0: return launch_fft_t<ROWS, true, false, false, 1>(a);
-        case 1: return launch_fft_t<ROWS, true, false, true, 1>(a);
-        case 2: return launch_fft_t<ROWS, true, true, false, 1>(a);
-        default: return launch_fft_t<ROWS, true, true, true, 1>(a);
+        case TAIL_BANK8_CHANNEL: return launch_fft_bank8<ROWS>(a, r);
+        case TAIL_BANK16_CHANNEL: return launch_fft_form<ROWS, true, TAIL_BANK16_CHANNEL>(a); // (per channel; arrays indexed by channel)
+        case TAIL_BANK16_ALL: return launch_fft_form<ROWS, true, TAIL_BANK16_ALL>(a, r.nco); // chan->out[] / rot0[] are indexed by SLOT
+        case TAIL_BANK4_OWN: return launch_fft_form<ROWS, true, TAIL_BANK4_OWN>(a);
+        case TAIL_BANK4_OWN_SUB: return launch_fft_form<ROWS, true, TAIL_BANK4_OWN_SUB>(a); // decimation 12, 20, 28, ...
+        case TAIL_BANK4_SLOTS: return launch_fft_form<ROWS, true, TAIL_BANK4_SLOTS>(a);
+        default: return hipErrorInvalidConfiguration;
         }
     }
-    else if (a.chan || (tail && !a.no_fold))
-        return hipErrorInvalidConfiguration; // 2 overlap rows: full-rate pipeline only (fft_overlap_rows never sends a tail here)
-    if (a.D == 1)
-        switch (key)
-        {
-        case 0: return launch_fft_t<ROWS, false, false, false>(a);
-        case 1: return launch_fft_t<ROWS, false, false, true>(a);
-        case 2: return launch_fft_t<ROWS, false, true, false>(a);
-        default: return launch_fft_t<ROWS, false, true, true>(a);
-        }
-    switch (key) // any other decimation: full-rate kernel + selecting store
-    {
-    case 0: return launch_fft_t<ROWS, false, false, false, false, true>(a);
-    case 1: return launch_fft_t<ROWS, false, false, true, false, true>(a);
-    case 2: return launch_fft_t<ROWS, false, true, false, false, true>(a);
-    default: return launch_fft_t<ROWS, false, true, true, false, true>(a);
-    }
+    if (tail_in_dec2_units(r.tail)) // decimation 2: frequency-domain fold + 2048-point inverse (round 3); 6, 10, ..., 62: keeping every sub-th output
+        return launch_fft_dec2_rows<ROWS>(a, r.tail, r.nco, false);
+    if (r.dec4 && r.tail == TAIL_FULL_OR_DEC4)
+        return launch_fft_form<ROWS, true, TAIL_FULL_OR_DEC4>(a, r.nco);
+    if (r.dec4) // decimation 8, 12, ..., 64: the decimate-by-4 tail keeping every sub-th output (tables as for decimation 4)
+        return launch_fft_form<ROWS, true, TAIL_DEC4_SUB>(a, r.nco);
+    if (!r.decn)
+        return launch_fft_form<ROWS, false, TAIL_FULL_OR_DEC4>(a, r.nco);
+    return launch_fft_form<ROWS, false, TAIL_FULL_OR_DEC4, true>(a, r.nco); // any other decimation: full-rate kernel + selecting store
 }
 
 #ifdef IF_FIR_FFT_ONLY // (development: ONE instantiation, e.g. -DIF_FIR_FFT_ONLY='4,true,false,false,17,false,false', to read its code)
 __attribute__((used)) static auto *const if_fir_fft_only_kernel = &fir_fft_kernel<IF_FIR_FFT_ONLY>;
 #else
-template hipError_t launch_fft_rows<IF_FIR_FFT_ROWS>(const LaunchArgs &a);
+template hipError_t launch_fft_rows<IF_FIR_FFT_ROWS>(const LaunchArgs &a, const FftRoute &r);
 #endif
 
 #if IF_FIR_FFT_ROWS == 32
@@ -296,45 +237,31 @@ template hipError_t launch_fft_rows<IF_FIR_FFT_ROWS>(const LaunchArgs &a);
 // decimating tails like shorter filters do (round 3), an odd one through the selecting store.  The history holds 4096
 // samples: 2048 of delay + the overlap.
 template <bool ACC>
-static hipError_t launch_fft_partition(const LaunchArgs &a)
+static hipError_t launch_fft_partition(const LaunchArgs &a, const FftRoute &r)
 {
-    int F = 1;
-    (void)fft_tail(a.T, a.D, &F, nullptr); // (a.T: the whole filter's tap count)
-    const int key = (a.in_i16 ? 2 : 0) | (a.nco_word ? 1 : 0);
-#define IF_FIR_PART_SWITCH(DEC4, CHAN, DECN)                                            \
-    switch (key)                                                                       \
-    {                                                                                  \
-    case 0: return launch_fft_t<32, DEC4, false, false, CHAN, DECN, ACC>(a);           \
-    case 1: return launch_fft_t<32, DEC4, false, true, CHAN, DECN, ACC>(a);            \
-    case 2: return launch_fft_t<32, DEC4, true, false, CHAN, DECN, ACC>(a);            \
-    default: return launch_fft_t<32, DEC4, true, true, CHAN, DECN, ACC>(a);            \
-    }
-    if (a.D == 1)
-        IF_FIR_PART_SWITCH(false, 0, false)
-    if (F == 4 && a.D == 4)
-        IF_FIR_PART_SWITCH(true, 0, false)
-    if (F == 4)
-        IF_FIR_PART_SWITCH(true, 1, false)
-    if (F == 2 && a.D == 2 && !a.no_fold)
-        return launch_fft_dec2_rows<32>(a, 2, key, ACC);
-    if (F == 2 && !a.no_fold)
-        return launch_fft_dec2_rows<32>(a, 3, key, ACC);
-    IF_FIR_PART_SWITCH(false, 0, true)
-#undef IF_FIR_PART_SWITCH
+    if (!r.dec4 && !r.decn)
+        return launch_fft_form<32, false, TAIL_FULL_OR_DEC4, false, ACC>(a, r.nco);
+    if (r.dec4 && r.tail == TAIL_FULL_OR_DEC4)
+        return launch_fft_form<32, true, TAIL_FULL_OR_DEC4, false, ACC>(a, r.nco);
+    if (r.tail == TAIL_DEC4_SUB)
+        return launch_fft_form<32, true, TAIL_DEC4_SUB, false, ACC>(a, r.nco);
+    if (tail_in_dec2_units(r.tail))
+        return launch_fft_dec2_rows<32>(a, r.tail, r.nco, ACC);
+    return launch_fft_form<32, false, TAIL_FULL_OR_DEC4, true, ACC>(a, r.nco);
 }
 
-hipError_t launch_fft_two_partitions(const LaunchArgs &a)
+hipError_t launch_fft_two_partitions(const LaunchArgs &a, const FftRoute &r)
 {
     if (a.chan || !a.fft_tables_b || a.hist_len < 2 * FFT_PART)
         return hipErrorInvalidConfiguration;
     LaunchArgs p = a;
-    const hipError_t e = launch_fft_partition<false>(p);
+    const hipError_t e = launch_fft_partition<false>(p, r);
     if (e != hipSuccess)
         return e;
     p.fft_tables = a.fft_tables_b;
     p.in_shift = FFT_PART;
     p.hist_out = nullptr; // the first launch wrote the next history
-    return launch_fft_partition<true>(p);
+    return launch_fft_partition<true>(p, r);
 }
 #endif // 32-row unit
 #endif // !IF_FIR_FFT_DEC2_UNIT

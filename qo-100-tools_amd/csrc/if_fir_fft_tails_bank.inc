@@ -1,6 +1,6 @@
 // if_fir_fft_tails_bank.inc -- part of the overlap-save kernel's source (if_fir_fft.hip includes it; not a translation unit of its own).
-// Filter-bank tails of fir_fft_kernel (CHAN = 16, 17, 9, 8, 4, 5, 6): included INSIDE the kernel body, behind the forward transform.
-        if constexpr (CHAN == 16)
+// Filter-bank tails of fir_fft_kernel (tail_is_bank: TAIL_BANK16_ALL, 16_CHANNEL, 8_ALL, 8_CHANNEL, 4_SLOTS, 4_OWN, 4_OWN_SUB = CHAN 16, 17, 9, 8, 4, 5, 6): included INSIDE the kernel body, behind the forward transform.
+        if constexpr (CHAN == TAIL_BANK16_ALL)
         {
             // ---- 16-slot filter bank at the channel rate (decimation 16, round 3; tools/fft_model.py bank16) --------------
             // Channel s = the prototype moved up by s/16 cycles/sample; decimating by 16 aliases every slot centre to DC.
@@ -83,7 +83,7 @@
                 }
             }
         }
-        else if constexpr (CHAN == 17)
+        else if constexpr (CHAN == TAIL_BANK16_CHANNEL)
         {
             // ---- filter bank at decimation 16, every channel at its own centre bin (round 4; the decimation-8 general form below at
             // the channel rate).  Centre bin B = 256 s + b: H_c(k) = H(k - B); with k = k_low + 256 k2 and k_low - b = kappa - 256 cy
@@ -214,7 +214,7 @@
                 }
             }
         }
-        else if constexpr (CHAN == 9)
+        else if constexpr (CHAN == TAIL_BANK8_ALL)
         {
             // ---- filter bank at decimation 8, ALL SLOTS OF ONE PARITY (round 4, VERDICT r3 #2; tools/fft_model.py bank8_parity) ----
             // Z_s(k2') = sum_a w_{k2'}[a] W16^(a s) G_q[a], q = (k2' - s) mod 2 (the per-channel form above).  For the slots of one parity,
@@ -332,7 +332,7 @@
                     refill();
             }
         }
-        else if constexpr (CHAN == 8)
+        else if constexpr (CHAN == TAIL_BANK8_CHANNEL)
         {
             // ---- filter bank at decimation 8 (fs/16 slots, 2x oversampled channels; tools/fft_model.py bank8) ------------
             // First radix-2 stage of pass 3 once, in place: r[phys(i, a)] = w0[a] = t[a] + t[a+8], r[phys(i, a+8)] = w1[a].
@@ -342,7 +342,7 @@
             // (cos, tan) form (round 4): the inputs of this pass still carry b^n2, b = W4096^(k0 + 16 k1);
             // t[a] b^a +- t[a + 8] b^(a + 8) = b^a (t[a] +- b^8 t[a + 8]): b^8 = c (1 + j t) is applied here (three packed FMAs a pair), b^a is
             // folded into the table for the lane that OWNS the entry (see the general form below for lanes that read another lane's)
-            static_assert(CHAN != 8 || TAN, "the decimation-8 bank is written for its (cos, tan) image");
+            static_assert(CHAN != TAIL_BANK8_CHANNEL || TAN, "the decimation-8 bank is written for its (cos, tan) image");
 #pragma unroll
             for (int i = 0; i < 4; i++)
             {
@@ -562,7 +562,7 @@
             }
             }
         }
-        else if constexpr (CHAN == 4)
+        else if constexpr (CHAN == TAIL_BANK4_SLOTS)
         {
             // ---- uniform filter bank (SURVEY §8f-2): one forward transform, one decimated inverse per channel ---------
             // Channel slot s = the prototype moved to s/16 cycles/sample and mixed down: H_s(k2) = H(k2 - s), so with the
@@ -665,7 +665,7 @@
                     buf_store(csrd, voff, (mu0 - MU0_FIRST) * 512, cmul_v<false>(c[mu0], wl));
             }
         }
-        else if constexpr (CHAN == 5 || CHAN == 6)
+        else if constexpr (CHAN == TAIL_BANK4_OWN || CHAN == TAIL_BANK4_OWN_SUB)
         {
             // ---- filter bank at decimation 4, every channel at its own centre bin (round 4) ---------------------------------------
             // The slot form above with the table entries of kappa (k_low - b = kappa - 256 cy, gathered from the lane that holds kappa)
@@ -680,7 +680,7 @@
 #pragma unroll
                 for (int j = 0; j < 16; j++)
                     t[j] = r[phys(i, j)];
-                static_assert((CHAN != 5 && CHAN != 6) || TAN, "the general form at decimation 4 is written for the (cos, tan) image");
+                static_assert((CHAN != TAIL_BANK4_OWN && CHAN != TAIL_BANK4_OWN_SUB) || TAN, "the general form at decimation 4 is written for the (cos, tan) image");
                 const cf e1 = tw1[(i * 3 + 0) * 64 + lane], e2 = tw1[(i * 3 + 1) * 64 + lane], e3 = tw1[(i * 3 + 2) * 64 + lane];
 #pragma unroll
                 for (int m0 = 0; m0 < 4; m0++)
@@ -763,7 +763,7 @@
                 lds_fetch<16 - MU0_FIRST, 1>(rowp, rowp_t); // (round 5: the channel's row phasors requested together, ahead of the store loop)
                 // decimation 12, 20, 28, ... (4 x sub): every sub-th output of this tail is a real output (KeepEvery, as in the
                 // single-channel tail; sub = 1: all of them).  Descriptor over the kept outputs from this block's first one on.
-                if constexpr (CHAN == 5) // (decimation 4 itself; its own instantiation: with both store loops in one kernel it ran 4 % slower)
+                if constexpr (CHAN == TAIL_BANK4_OWN) // (decimation 4 itself; its own instantiation: with both store loops in one kernel it ran 4 % slower)
                 {
                     const srd_t csrd = make_srd(chan.out[ch] + obase, (diag & 2) ? 0 : (M - obase) * 8);
 #pragma unroll

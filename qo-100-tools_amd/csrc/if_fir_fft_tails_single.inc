@@ -1,6 +1,6 @@
 // if_fir_fft_tails_single.inc -- part of the overlap-save kernel's source (if_fir_fft.hip includes it; not a translation unit of its own).
 // Single-channel tails of fir_fft_kernel (decimate-by-2 and its multiples, decimate-by-4 and its multiples, full rate / selecting store): included INSIDE the kernel body.
-        if constexpr (CHAN == 2 || CHAN == 3)
+        if constexpr (tail_in_dec2_units(CHAN))
         {
             // ---- decimate-by-2 tail (round 3): pass 3, multiply by H/4096, fold the 2 aliases
             // (k2 = k2' + 8 j) in place: r[phys(i, k2')] = z(i, k2'), k2' = 0..7; the other 8 registers of the group are dead
@@ -114,7 +114,7 @@
                     co[mu0] = cmul_v<false>(co[mu0], cmul_v<false>(a_odd, ncob[4 * (mu0 - MU0_FIRST)]));
                 }
             }
-            if constexpr (CHAN == 3)
+            if constexpr (CHAN == TAIL_DEC2_SUB)
             {
                 // decimation 6, 10, ..., 62 (2 x odd): every sub-th output of this tail is a real output (KeepEvery, as behind the
                 // decimate-by-4 tail); the pair of a lane never survives together, so two 8-byte stores with their own offsets.
@@ -150,7 +150,7 @@
                         load_row<I16, LAUX, EDGE>(r, nsrd, lane, phys(i, j));
             }
             unsigned vo128 = (unsigned)lane * 16u;
-            if constexpr (CHAN == 2)
+            if constexpr (CHAN == TAIL_DEC2)
             {
 #pragma unroll
             for (int mu0 = MU0_FIRST; mu0 < 16; mu0++)
@@ -274,7 +274,7 @@
                 for (int mu0 = MU0_FIRST; mu0 < 16; mu0++)
                     c[mu0] = cmul_v<false>(c[mu0], cmul_v<false>(a_lane, ncob[mu0 - MU0_FIRST]));
             }
-            if constexpr (CHAN == 1)
+            if constexpr (CHAN == TAIL_DEC4_SUB)
             {
                 // decimation 8, 12, ..., 64: every sub-th output of the decimate-by-4 tail is a real output.  Descriptor over the
                 // kept outputs from this block's first one on (decn_m of them in the call); a lane that keeps nothing, or an

@@ -5,6 +5,8 @@
 
 #include <mutex>
 
+#include "if_fir_fft_route.h" // the overlap-save backend's routing: named tails, predicates (fft_supported, fft_tail, ...), fft_route
+
 namespace if_fir
 {
 
@@ -123,29 +125,17 @@ inline hipError_t device_setup(DeviceSetup &d, int device, const void *kern, int
 
 bool direct_supported(int T, int D);
 hipError_t launch_fir(const LaunchArgs &a, int variant);
-// overlap-save FFT backend (if_fir_fft.hip)
-constexpr int FFT_TABLE_FLOATS = 2 * (4096 + 4096 + 256 + 1024 + 1024 + 64 + 256); // ... + 64 NCO row phasors + 256 W2048 twiddles
-bool fft_supported(int T, int D);
-bool fft_two_partitions(int T); // 3074..4096 taps: two launches (2048 + the rest), see launch_fft
+// overlap-save FFT backend (if_fir_fft.hip); which kernel and table image serve a call: if_fir_fft_route.h
 hipError_t launch_fft(const LaunchArgs &a);
-// bank = 8 / 16: the merged table of the filter bank at decimation 8 / 16 in place of H; full_rate (D != 4, no bank): the image of
-// the full-rate pipeline (D = 1, the selecting store) with its twiddles in (cos, tan) form -- the decimate-by-2 tails keep the plain one
-int fft_bank_tail(int D, bool general);
-void fft_bank8_plan(const uint32_t *slots, uint32_t count, bool all_slots_available, uint32_t pmask[2], uint32_t *rest);
-void fft_build_tables(const float *taps, int T, int ctaps, int D, uint32_t nco_delta, double in_scale, float *tables,
-                      int bank = 0, int full_rate = 0, int bank_parity = 0);
-
-// Odd decimations F x sub, F = 3 or 5 (round 4): blocks of F x 1024 input samples, F forward 1024-point transforms of the phase
-// streams and one inverse (fir_odd_kernel); *pOvlr = dropped 64-output rows of a block (2, 4 or 8).  False: no such tail (the
-// full-rate pipeline + selecting store serves the pair).
-bool fft_odd_tail(int T, int D, int *pF, int *pSub, int *pOvlr);
-constexpr int fft_odd_table_floats(int F) { return 2 * (F * 1024 + 256 + 768 + 1024 + 64 + 64 + 256); } // G_p | TB | TC | TWD | TWE | NCO | phasor tables (round 5)
+inline FftRoute fft_route_of(const LaunchArgs &a)
+{
+    return fft_route(a.T, a.D, !a.chan ? FFT_NO_BANK : a.chan->general ? FFT_BANK_OWN_CENTRES : FFT_BANK_SLOTS, a.nco_word != 0, a.no_fold != 0);
+}
+// one table image of FFT_TABLE_FLOATS floats (image.kind other than FFT_IMAGE_ODD; FFT_IMAGE_BANK8: the one of image.parity)
+void fft_build_tables(const float *taps, int T, int ctaps, const FftImage &image, uint32_t nco_delta, double in_scale, float *tables);
+// odd decimations F x sub, F = 3 (round 4, fir_odd_kernel): blocks of F x 1024 input samples, F forward 1024-point transforms, one inverse
 void fft_build_tables_odd(const float *taps, int T, int ctaps, int F, uint32_t nco_delta, double in_scale, float *tables);
 hipError_t launch_fft_odd(const LaunchArgs &a);
-int fft_overlap_rows(int T, int D);
-int fft_block_advance(int T, int D); // new input samples per block: the unit at which a stream can be cut without changing a bit
-// decimating tail of (T, D): D = F * sub, F = 2 or 4 the tail's own decimation (false, F = 1: full-rate kernel + selecting store)
-bool fft_tail(int T, int D, int *pF, int *pSub);
 // history buffers hold the last `hist_len` samples of the stream (>= T-1; hist_in/hist_out: whole buffers)
 hipError_t launch_history(const void *in, const void *hist_in, void *hist_out, int hist_len, int64_t N, int in_i16,
                           hipStream_t stream);

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "if_fir.h"
+#include "if_fir_fft_route.h" // fft_tail, fft_odd_tail, fft_block_advance
 #ifdef IF_FIR_DEVELOPMENT
 #include "if_fir_debug.h"
 #endif
@@ -102,12 +103,6 @@ thread_local char g_mc_init_err[256] = "";
 constexpr uint64_t MC_CHUNK_DEFAULT = 16773120; // 78 x 215 040 (round 3's global unit, the lcm of the block advances then)
 } // namespace
 
-namespace if_fir
-{
-bool fft_tail(int T, int D, int *pF, int *pSub); // if_fir_fft.hip
-bool fft_odd_tail(int T, int D, int *pF, int *pSub, int *pOvlr);
-int fft_block_advance(int T, int D);
-}
 // internal to the library (if_fir_shim.cpp, hidden): device address of the context's queue fault counter
 extern "C" __attribute__((visibility("hidden"))) const uint32_t *if_fir_internal_fault_word(const if_fir_ctx_t *pCtx);
 

@@ -23,6 +23,28 @@
 
 #define IF_FIR_API extern "C" __attribute__((visibility("default")))
 
+// A tuning variant of if_fir_set_tuning, decoded (if_fir_debug.h lists the development ones; the production library accepts 0..6 only)
+struct Tuning
+{
+    int schedule;        // 0..6: schedule variant of the direct kernels
+    uint32_t diag;       // 1000 + bits / 1000000 + bits: diagnostic bits of the overlap-save launch
+    int grid_limit;      // 2000 + k: at most k workgroups for the overlap-save kernel
+    bool no_fold;        // 3000: no odd-decimation kernel and no decimate-by-2 tail, the full-rate kernel + selecting store instead
+    bool inject_failure; // 4000: the next call fails before anything is launched
+    bool needs_debug;    // a diagnostic launch (wrong results) or the injected failure: refused unless IF_FIR_DEBUG=1
+};
+static Tuning decode_tuning(uint32_t v)
+{
+    Tuning t{};
+    t.schedule = v <= 6 ? (int)v : 0;
+    t.diag = (v >= 1000 && v < 2000) ? v - 1000 : (v >= 1000000 && v < 3000000) ? v - 1000000 : 0;
+    t.grid_limit = (v > 2000 && v < 3000) ? (int)(v - 2000) : 0;
+    t.no_fold = v == 3000;
+    t.inject_failure = v == 4000;
+    t.needs_debug = (v >= 1000 && v < 2000) || v == 4000 || v >= 1000000;
+    return t;
+}
+
 struct if_fir_ctx
 {
     int device;
@@ -33,7 +55,7 @@ struct if_fir_ctx
     int in_i16; // input format: 0 = float32 I,Q; 1 = int16 I,Q
     uint32_t backend_req;
     uint32_t backend;
-    int variant;
+    Tuning tuning;
     float *d_taps;
     void *d_hist[2]; // the last hist_len samples of the stream (raw input format), ping-pong
     int hist_len;    // max(T-1, the overlap-save block overlap): see hist_len_for()
@@ -47,7 +69,6 @@ struct if_fir_ctx
     uint32_t chunk_ev_count;
     float tone[10];
     float *h_taps; // host copy of the caller's taps (FFT tables are built on demand)
-    bool tables_odd;   // d_fft_tables holds the odd-decimation kernel's image (ensure_fft_tables)
     uint32_t nco_word; // SPEC §3.2 phase word (0 = no NCO)
     float *h_eff; // NCO on: effective complex taps g[k] = h[k] e^{+j theta k} (2T floats), else nullptr
     void *d_fft_tables; // overlap-save backend tables (built on first use)
@@ -87,15 +108,8 @@ static void set_err(const if_fir_ctx *ctx, const char *fmt, ...)
 static inline int eff_ctaps(const if_fir_ctx *ctx) { return ctx->ctaps || ctx->nco_word; }
 static inline const float *eff_taps(const if_fir_ctx *ctx) { return ctx->h_eff ? ctx->h_eff : ctx->h_taps; }
 
-// The decimating tail of this context's (taps, decimation): D = F * sub (if_fir::fft_tail; F = 1: none)
-static inline int tail_factor(const if_fir_ctx *ctx, int *psub = nullptr)
-{
-    int F = 1, sub = 1;
-    if_fir::fft_tail(ctx->T, ctx->D, &F, &sub);
-    if (psub)
-        *psub = sub;
-    return F;
-}
+// the route of this context's single-channel calls (if_fir_fft_route.h): kernel family, tail, table image
+static inline if_fir::FftRoute ctx_route(const if_fir_ctx *ctx, bool no_fold) { return if_fir::fft_route(ctx->T, ctx->D, if_fir::FFT_NO_BANK, ctx->nco_word != 0, no_fold); }
 
 // AUTO: the fastest backend that meets SPEC §3.  Measured over (taps, decimation) from 3 taps to 4095 and decimation
 // 1 to 64 (tools/policy_sweep.py, profiles/r01d_policy_sweep.txt, r02_policy_sweep.txt) the overlap-save kernel wins
@@ -120,15 +134,9 @@ static uint32_t resolve_backend(const if_fir_ctx *ctx, uint32_t req)
 static int hist_len_for(int T, int D)
 {
     const int need = T > 1 ? T - 1 : 0;
-    if (!if_fir::fft_supported(T, 1))
-        return need;
-    if (if_fir::fft_two_partitions(T))
-        return 4096; // second partition: 2048 samples of delay + the 2048-sample block overlap
-    int ovl = 64 * if_fir::fft_overlap_rows(T, 4); // (the longest overlap any decimation of this filter uses)
-    int F = 1, ovlr = 0;
-    if (if_fir::fft_odd_tail(T, D, &F, nullptr, &ovlr) && F * 64 * ovlr > ovl)
-        ovl = F * 64 * ovlr; // the odd-decimation kernel's blocks (F x 1024 samples) overlap by F x 64 x ovlr input samples
-    return ovl > need ? ovl : need;
+    // (either route of the pair, the default one and the development variant 3000's: the longest overlap this filter uses)
+    const int a = if_fir::fft_route(T, D, if_fir::FFT_NO_BANK, false, false).hist_need, b = if_fir::fft_route(T, D, if_fir::FFT_NO_BANK, false, true).hist_need;
+    return need > a && need > b ? need : a > b ? a : b;
 }
 
 #ifdef IF_FIR_DEVELOPMENT
@@ -141,8 +149,7 @@ static bool debug_enabled()
 // such bit belonged to a closed experiment, and a launch with it would silently run the default
 static uint32_t retired_diag_bits(uint32_t v)
 {
-    const uint32_t diag = (v >= 1000 && v < 2000) ? v - 1000 : (v >= 1000000 && v < 3000000) ? v - 1000000 : 0;
-    return diag & ~(1u | 2u | 256u | 512u | 4096u | 8192u | 131072u | 262144u);
+    return decode_tuning(v).diag & ~(1u | 2u | 256u | 512u | 4096u | 8192u | 131072u | 262144u);
 }
 #endif
 
@@ -164,102 +171,61 @@ static bool backend_ok(const if_fir_ctx *ctx, uint32_t b)
     }
 }
 
-// twiddles and FFT(taps)/4096 in the kernel's LDS image order, float64 math on the host, once per context
-static uint8_t ensure_fft_tables(if_fir_ctx *ctx)
+// The table images of a route in one device buffer (*dst), built on first use: twiddles and FFT(taps)/4096 in the kernel's LDS image
+// order, float64 math on the host.  Two images back to back for the two partitions (2048 taps + the rest) of 3074..4096 taps, and
+// for the bank at decimation 8 (its own -- per-channel forms, the all-slots form's even slots -- and the all-slots form's for the
+// odd slots, round 4).
+static uint8_t ensure_tables(if_fir_ctx *ctx, void **dst, const if_fir::FftRoute &route, const char *what)
 {
-    if (ctx->d_fft_tables)
+    if (*dst)
         return 1;
-    // 3074..4096 taps run as two partitions (2048 taps + the rest): two table images back to back
-    const bool two = if_fir::fft_two_partitions(ctx->T);
-    // odd decimations 3, 9, 15, ... (round 4): the image of fir_odd_kernel (development variant 3000 = the full-rate pipeline with
-    // a selecting store instead, on the ordinary image; if_fir_set_tuning drops the tables when it crosses that line)
-    int oddF = 1;
-    const bool odd = if_fir::fft_odd_tail(ctx->T, ctx->D, &oddF, nullptr, nullptr) && ctx->variant != 3000;
-    const size_t tab_floats = odd ? (size_t)if_fir::fft_odd_table_floats(oddF) : (size_t)if_fir::FFT_TABLE_FLOATS * (two ? 2 : 1);
-    float *tab = (float *)malloc(sizeof(float) * tab_floats);
+    if_fir::FftImage image = route.image;
+    float *tab = (float *)malloc(sizeof(float) * (size_t)image.floats);
     if (!tab)
     {
-        set_err(ctx, "overlap-save tables: out of host memory");
+        set_err(ctx, "%s tables: out of host memory", what);
         return 0;
     }
-    ctx->tables_odd = odd;
-    // NCO row phasors: per kept output for the decimate-by-4 kernel, per full-rate output for all others
     // int16 input: the kernel leaves the samples unscaled and the table carries the format's 2^-15
-    // decimation 4 and its multiples (8, 12, ..., 64: the same tail keeping every sub-th output) take the merged table and
-    // NCO row steps of decimation 4; decimation 2 (and 6, 10, ...) and the selecting-store route the plain one
-    const int F = tail_factor(ctx);
-    const int tabD = F == 4 ? 4 : 1;
-    // D = 1 and the selecting store (odd decimations; development variant 3000: decimation 2, 6, 10, ... on it as well): the
-    // full-rate pipeline's image
-    const int full = (F == 1 || (F == 2 && ctx->variant == 3000)) ? 1 : 0;
-    const uint32_t tab_nco = 0u - ctx->nco_word * (F == 4 ? 4u : 1u);
-    if (odd)
-        if_fir::fft_build_tables_odd(eff_taps(ctx), ctx->T, eff_ctaps(ctx), oddF, 0u - ctx->nco_word * (uint32_t)oddF,
-                                     ctx->in_i16 ? 0x1p-15 : 1.0, tab);
-    else if (two)
-    {
-        // two partitions: each a filter of <= 2048 taps with its own table image
-        const int step = eff_ctaps(ctx) ? 2 : 1, part = 2048;
-        if_fir::fft_build_tables(eff_taps(ctx), part, eff_ctaps(ctx), tabD, tab_nco, ctx->in_i16 ? 0x1p-15 : 1.0, tab, 0, full);
-        if_fir::fft_build_tables(eff_taps(ctx) + (size_t)step * part, ctx->T - part, eff_ctaps(ctx), tabD, tab_nco,
-                                 ctx->in_i16 ? 0x1p-15 : 1.0, tab + if_fir::FFT_TABLE_FLOATS, 0, full);
-    }
+    const double scale = ctx->in_i16 ? 0x1p-15 : 1.0;
+    const uint32_t tab_nco = 0u - ctx->nco_word * (uint32_t)image.nco_step;
+    const bool parts = route.family == if_fir::FFT_FAMILY_TWO_PARTITIONS; // each a filter of <= FFT_PART taps with its own image
+    if (image.kind == if_fir::FFT_IMAGE_ODD)
+        if_fir::fft_build_tables_odd(eff_taps(ctx), ctx->T, eff_ctaps(ctx), route.F, tab_nco, scale, tab);
     else
-        if_fir::fft_build_tables(eff_taps(ctx), ctx->T, eff_ctaps(ctx), tabD, tab_nco, ctx->in_i16 ? 0x1p-15 : 1.0, tab, 0, full);
+        for (int i = 0; i < image.images; i++)
+        {
+            const int first = parts ? i * if_fir::FFT_PART : 0, count = !parts ? ctx->T : i ? ctx->T - first : if_fir::FFT_PART;
+            image.parity = parts ? 0 : i;
+            if_fir::fft_build_tables(eff_taps(ctx) + (size_t)(eff_ctaps(ctx) ? 2 : 1) * first, count, eff_ctaps(ctx), image, tab_nco, scale,
+                                     tab + (size_t)i * if_fir::FFT_TABLE_FLOATS);
+        }
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess)
-        e = hipMalloc(&ctx->d_fft_tables, sizeof(float) * tab_floats);
+        e = hipMalloc(dst, sizeof(float) * (size_t)image.floats);
     if (e == hipSuccess)
-        e = hipMemcpy(ctx->d_fft_tables, tab, sizeof(float) * tab_floats, hipMemcpyHostToDevice);
+        e = hipMemcpy(*dst, tab, sizeof(float) * (size_t)image.floats, hipMemcpyHostToDevice);
     free(tab);
     if (e != hipSuccess)
     {
         // never leave an allocated but unfilled image behind: the next call would take it for the tables
-        if (ctx->d_fft_tables)
-            (void)hipFree(ctx->d_fft_tables);
-        ctx->d_fft_tables = nullptr;
-        set_err(ctx, "overlap-save tables: upload failed: %s", hipGetErrorString(e));
+        if (*dst)
+            (void)hipFree(*dst);
+        *dst = nullptr;
+        set_err(ctx, "%s tables: upload failed: %s", what, hipGetErrorString(e));
         return 0;
     }
     return 1;
 }
-
-// merged table image of the filter bank at decimation 8 or 16
+// the context's own image: its single-channel route's (development variant 3000: if_fir_set_tuning drops the tables when the image changes)
+static uint8_t ensure_fft_tables(if_fir_ctx *ctx)
+{
+    return ensure_tables(ctx, &ctx->d_fft_tables, ctx_route(ctx, ctx->tuning.no_fold), "overlap-save");
+}
+// merged table image of the filter bank at decimation 8 or 16 (themselves, or the tail behind 24, 32, ..., 64)
 static uint8_t ensure_bank_tables(if_fir_ctx *ctx)
 {
-    if (ctx->d_fft_tables_bank)
-        return 1;
-    // decimation 8: two images back to back -- the bank's own (per-channel forms, and the all-slots form's even slots) and the
-    // all-slots form's for the odd slots (round 4)
-    const int bank = if_fir::fft_bank_tail(ctx->D, true); // 8 or 16 (decimation 8 / 16 themselves, or the tail behind 24, 32, ..., 64)
-    const size_t images = bank == 8 ? 2 : 1;
-    float *tab = (float *)malloc(sizeof(float) * if_fir::FFT_TABLE_FLOATS * images);
-    if (!tab)
-    {
-        set_err(ctx, "filter-bank tables: out of host memory");
-        return 0;
-    }
-    // (the NCO's effective complex taps and its per-output phase step, like the single-channel tables)
-    if_fir::fft_build_tables(eff_taps(ctx), ctx->T, eff_ctaps(ctx), ctx->D, 0u - ctx->nco_word * (uint32_t)bank,
-                             ctx->in_i16 ? 0x1p-15 : 1.0, tab, bank);
-    if (images == 2)
-        if_fir::fft_build_tables(eff_taps(ctx), ctx->T, eff_ctaps(ctx), ctx->D, 0u - ctx->nco_word * (uint32_t)bank,
-                                 ctx->in_i16 ? 0x1p-15 : 1.0, tab + if_fir::FFT_TABLE_FLOATS, bank, 0, 1);
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess)
-        e = hipMalloc(&ctx->d_fft_tables_bank, sizeof(float) * if_fir::FFT_TABLE_FLOATS * images);
-    if (e == hipSuccess)
-        e = hipMemcpy(ctx->d_fft_tables_bank, tab, sizeof(float) * if_fir::FFT_TABLE_FLOATS * images, hipMemcpyHostToDevice);
-    free(tab);
-    if (e != hipSuccess)
-    {
-        if (ctx->d_fft_tables_bank)
-            (void)hipFree(ctx->d_fft_tables_bank);
-        ctx->d_fft_tables_bank = nullptr;
-        set_err(ctx, "filter-bank tables: upload failed: %s", hipGetErrorString(e));
-        return 0;
-    }
-    return 1;
+    return ensure_tables(ctx, &ctx->d_fft_tables_bank, if_fir::fft_route(ctx->T, ctx->D, if_fir::FFT_BANK_OWN_CENTRES, false, false), "filter-bank");
 }
 
 static void tone_table(float *t)
@@ -375,11 +341,12 @@ static uint8_t init_common(if_fir_ctx_t **ppCtx, const float *pfTaps, uint32_t u
 #ifdef IF_FIR_DEVELOPMENT
     // development library only: IF_FIR_DEBUG=1 IF_FIR_VARIANT=n preselects a tuning variant
     const char *v = debug_enabled() ? getenv("IF_FIR_VARIANT") : nullptr;
-    ctx->variant = v ? atoi(v) : 0;
-    if (retired_diag_bits((uint32_t)ctx->variant))
+    const int variant = v ? atoi(v) : 0;
+    ctx->tuning = decode_tuning((uint32_t)variant);
+    if (retired_diag_bits((uint32_t)variant))
     {
         snprintf(g_init_err, sizeof(g_init_err), "if_fir_init: IF_FIR_VARIANT=%d carries retired diagnostic bits (if_fir_debug.h)",
-                 ctx->variant);
+                 variant);
         if_fir_destroy(ctx);
         return 0;
     }
@@ -500,7 +467,7 @@ IF_FIR_API uint8_t if_fir_set_tuning(if_fir_ctx_t *pCtx, uint32_t ulVariant)
     }
     // diagnostic launches of the overlap-save kernel skip loads or stores (WRONG results, for timing studies) and 4000 injects
     // a failure: refused unless the process runs with IF_FIR_DEBUG=1
-    if (((ulVariant >= 1000 && ulVariant < 2000) || ulVariant == 4000 || ulVariant >= 1000000) && !debug_enabled())
+    if (decode_tuning(ulVariant).needs_debug && !debug_enabled())
     {
         set_err(pCtx, "if_fir_set_tuning: variant %u is a diagnostic launch (wrong results); set IF_FIR_DEBUG=1 to allow it",
                 ulVariant);
@@ -514,18 +481,16 @@ IF_FIR_API uint8_t if_fir_set_tuning(if_fir_ctx_t *pCtx, uint32_t ulVariant)
         return 0;
     }
 #endif
-    int tailF = 1;
-    (void)if_fir::fft_tail(pCtx->T, pCtx->D, &tailF, nullptr);
-    if (((int)ulVariant == 3000) != (pCtx->variant == 3000) && pCtx->d_fft_tables &&
-        (if_fir::fft_odd_tail(pCtx->T, pCtx->D, nullptr, nullptr, nullptr) || tailF == 2))
+    const Tuning tuning = decode_tuning(ulVariant);
+    if (pCtx->d_fft_tables && ctx_route(pCtx, tuning.no_fold).image.kind != ctx_route(pCtx, pCtx->tuning.no_fold).image.kind)
     {
-        // the selecting-store route and the odd-decimation kernel take different table images: rebuilt on the next call
+        // the selecting-store route takes another table image than the odd-decimation kernel and the decimate-by-2 tails: rebuilt on the next call
         HIP_TRY(pCtx, hipSetDevice(pCtx->device));
         HIP_TRY(pCtx, hipStreamSynchronize(pCtx->stream));
         (void)hipFree(pCtx->d_fft_tables);
         pCtx->d_fft_tables = nullptr;
     }
-    pCtx->variant = (int)ulVariant;
+    pCtx->tuning = tuning;
     return 1;
 }
 
@@ -610,11 +575,11 @@ static uint8_t run_device(if_fir_ctx *ctx, const void *in, void *out, uint64_t n
         return 0;
     }
 #ifdef IF_FIR_DEVELOPMENT
-    if (ctx->variant == 4000 && debug_enabled())
+    if (ctx->tuning.inject_failure && debug_enabled())
     {
         // test hook (dev library, IF_FIR_DEBUG=1): the next call fails before anything is launched -- lets the tests exercise
         // the error paths of callers (the multi-channel front's status word) without breaking a device
-        ctx->variant = 0;
+        ctx->tuning = Tuning{};
         set_err(ctx, "if_fir_process_device: injected failure (tuning variant 4000, test hook)");
         return 0;
     }
@@ -674,12 +639,11 @@ static uint8_t run_device(if_fir_ctx *ctx, const void *in, void *out, uint64_t n
     a.queue = ctx->d_queue;
 #ifdef IF_FIR_DEVELOPMENT
     a.dbg = ctx->d_dbg;
-    // FFT tuning variants (if_fir_debug.h): 1000 + bits / 1000000 + bits = diagnostics, 2000 + k = at most k workgroups
+    // the overlap-save launch's development switches (if_fir_debug.h)
     const bool fft_var = ctx->backend == IF_FIR_BACKEND_HIP_FFT;
-    a.diag = (fft_var && ctx->variant >= 1000 && ctx->variant < 2000) ? ctx->variant - 1000
-             : (fft_var && ctx->variant >= 1000000 && ctx->variant < 3000000) ? ctx->variant - 1000000 : 0;
-    a.grid_limit = (fft_var && ctx->variant > 2000 && ctx->variant < 3000) ? ctx->variant - 2000 : 0;
-    a.no_fold = ctx->variant == 3000;
+    a.diag = fft_var ? (int)ctx->tuning.diag : 0;
+    a.grid_limit = fft_var ? ctx->tuning.grid_limit : 0;
+    a.no_fold = ctx->tuning.no_fold;
 #endif
     if (chan)
     {
@@ -703,10 +667,10 @@ static uint8_t run_device(if_fir_ctx *ctx, const void *in, void *out, uint64_t n
         }
         chan->abs0n0 = (uint32_t)(ctx->consumed + n0);
         a.chan = chan;
-        const int fb = if_fir::fft_bank_tail(ctx->D, chan->general != 0);
-        if (fb >= 8)
+        const int kind = if_fir::fft_route_of(a).image.kind; // (the bank at decimation 4 runs on the context's own image)
+        if (kind == if_fir::FFT_IMAGE_BANK8 || kind == if_fir::FFT_IMAGE_BANK16)
             a.fft_tables = ctx->d_fft_tables_bank;
-        if (fb == 8) // (the all-slots form's image for the odd slots)
+        if (kind == if_fir::FFT_IMAGE_BANK8) // (the all-slots form's image for the odd slots)
             a.fft_tables_b = static_cast<const float *>(ctx->d_fft_tables_bank) + if_fir::FFT_TABLE_FLOATS;
     }
     a.queue_base = &ctx->queue_base;
@@ -717,7 +681,7 @@ static uint8_t run_device(if_fir_ctx *ctx, const void *in, void *out, uint64_t n
     if (ctx->backend == IF_FIR_BACKEND_HIP_FFT)
         HIP_TRY(ctx, if_fir::launch_fft(a));
     else
-        HIP_TRY(ctx, if_fir::launch_fir(a, ctx->variant));
+        HIP_TRY(ctx, if_fir::launch_fir(a, ctx->tuning.schedule));
     if (!fused_history)
         HIP_TRY(ctx, if_fir::launch_history(in, ctx->d_hist[ctx->hist_cur], ctx->d_hist[ctx->hist_cur ^ 1], ctx->hist_len,
                                             (int64_t)n, ctx->in_i16, ctx->stream));
@@ -1011,11 +975,12 @@ IF_FIR_API uint32_t if_fir_debug_fft_tables(const float *pfTaps, uint32_t ulTaps
     if (!pfTaps || !pfOut || ulOutFloats < (uint32_t)if_fir::FFT_TABLE_FLOATS ||
         !if_fir::fft_supported((int)ulTaps, (int)ulDecimation) || if_fir::fft_two_partitions((int)ulTaps))
         return 0; // (a two-partition filter is two such images, one per partition of <= 2048 taps)
-    // (the image the library would upload for this pair: decimation 4 and its multiples take the merged table, D = 1 and the
-    // selecting store the full-rate pipeline's, decimation 2, 6, 10, ... the plain one)
-    int F = 1;
-    if_fir::fft_tail((int)ulTaps, (int)ulDecimation, &F, nullptr);
-    if_fir::fft_build_tables(pfTaps, (int)ulTaps, bComplexTaps ? 1 : 0, F == 4 ? 4 : 1, ulNcoDelta, 1.0, pfOut, 0, F == 1 ? 1 : 0);
+    // (the image of the pair's DEFAULT route -- the hook has no variant argument; where that is the odd-decimation kernel, whose image
+    // if_fir_debug_fft_tables_odd returns, the selecting-store route's)
+    if_fir::FftImage image = if_fir::fft_route((int)ulTaps, (int)ulDecimation, if_fir::FFT_NO_BANK, false, false).image;
+    if (image.kind == if_fir::FFT_IMAGE_ODD)
+        image = if_fir::fft_route((int)ulTaps, (int)ulDecimation, if_fir::FFT_NO_BANK, false, true).image;
+    if_fir::fft_build_tables(pfTaps, (int)ulTaps, bComplexTaps ? 1 : 0, image, ulNcoDelta, 1.0, pfOut);
     return (uint32_t)if_fir::FFT_TABLE_FLOATS;
 }
 
@@ -1027,7 +992,9 @@ IF_FIR_API uint32_t if_fir_debug_fft_tables_bank(const float *pfTaps, uint32_t u
     if (!pfTaps || !pfOut || ulOutFloats < (uint32_t)if_fir::FFT_TABLE_FLOATS || (ulBank != 8 && ulBank != 16) ||
         !if_fir::fft_supported((int)ulTaps, (int)ulBank) || if_fir::fft_two_partitions((int)ulTaps))
         return 0;
-    if_fir::fft_build_tables(pfTaps, (int)ulTaps, bComplexTaps ? 1 : 0, (int)ulBank, 0u, 1.0, pfOut, (int)ulBank, 0, ulParity ? 1 : 0);
+    if_fir::FftImage image = if_fir::fft_route((int)ulTaps, (int)ulBank, if_fir::FFT_BANK_SLOTS, false, false).image;
+    image.parity = ulParity ? 1 : 0;
+    if_fir::fft_build_tables(pfTaps, (int)ulTaps, bComplexTaps ? 1 : 0, image, 0u, 1.0, pfOut);
     return (uint32_t)if_fir::FFT_TABLE_FLOATS;
 }
 IF_FIR_API uint32_t if_fir_debug_bank_tail(uint32_t ulDecimation, uint32_t bOwnCentres)

@@ -18,19 +18,18 @@ int main()
     for (int T : Ts)
         for (int ct = 0; ct < 2; ct++)
         {
-            for (int D : {1, 2, 4})
-                for (int full = 0; full < 2; full++)
-                {
-                    float *t = (float *)malloc(sizeof(float) * FFT_TABLE_FLOATS);
-                    fft_build_tables(taps.data(), T > 2049 ? 2048 : T, ct, D, 12345u, 1.0, t, 0, full, 0);
-                    free(t);
-                }
+            for (int kind : {FFT_IMAGE_PLAIN, FFT_IMAGE_FULL_RATE, FFT_IMAGE_DEC4})
+            {
+                float *t = (float *)malloc(sizeof(float) * FFT_TABLE_FLOATS);
+                fft_build_tables(taps.data(), T > 2049 ? 2048 : T, ct, FftImage{kind, 0, 1, FFT_TABLE_FLOATS, 1}, 12345u, 1.0, t);
+                free(t);
+            }
             if (T <= 3073)
-                for (int bank : {8, 16})
+                for (int kind : {FFT_IMAGE_BANK8, FFT_IMAGE_BANK16})
                     for (int par = 0; par < 2; par++)
                     {
                         float *t = (float *)malloc(sizeof(float) * FFT_TABLE_FLOATS);
-                        fft_build_tables(taps.data(), T, ct, bank, 777u, 1.0, t, bank, 0, par);
+                        fft_build_tables(taps.data(), T, ct, FftImage{kind, par, 1, FFT_TABLE_FLOATS, 8}, 777u, 1.0, t);
                         free(t);
                     }
             int F = 0, sub = 0, ovlr = 0;
@@ -58,12 +57,12 @@ int main()
 #include <hip/hip_runtime.h>
 namespace if_fir
 {
-template <int ROWS> hipError_t launch_fft_rows(const LaunchArgs &);
-template <> hipError_t launch_fft_rows<4>(const LaunchArgs &) { return hipErrorUnknown; }
-template <> hipError_t launch_fft_rows<8>(const LaunchArgs &) { return hipErrorUnknown; }
-template <> hipError_t launch_fft_rows<16>(const LaunchArgs &) { return hipErrorUnknown; }
-template <> hipError_t launch_fft_rows<32>(const LaunchArgs &) { return hipErrorUnknown; }
-template <> hipError_t launch_fft_rows<48>(const LaunchArgs &) { return hipErrorUnknown; }
-hipError_t launch_fft_two_partitions(const LaunchArgs &) { return hipErrorUnknown; }
+template <int ROWS> hipError_t launch_fft_rows(const LaunchArgs &, const FftRoute &);
+template <> hipError_t launch_fft_rows<4>(const LaunchArgs &, const FftRoute &) { return hipErrorUnknown; }
+template <> hipError_t launch_fft_rows<8>(const LaunchArgs &, const FftRoute &) { return hipErrorUnknown; }
+template <> hipError_t launch_fft_rows<16>(const LaunchArgs &, const FftRoute &) { return hipErrorUnknown; }
+template <> hipError_t launch_fft_rows<32>(const LaunchArgs &, const FftRoute &) { return hipErrorUnknown; }
+template <> hipError_t launch_fft_rows<48>(const LaunchArgs &, const FftRoute &) { return hipErrorUnknown; }
+hipError_t launch_fft_two_partitions(const LaunchArgs &, const FftRoute &) { return hipErrorUnknown; }
 hipError_t launch_fft_odd(const LaunchArgs &) { return hipErrorUnknown; }
 }

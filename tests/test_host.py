@@ -420,6 +420,22 @@ def test_block_queue_kernel_code_under_host_simulation():
     assert run.returncode == 0 and "(groups " in run.stdout, run.stdout
 
 
+def test_overlap_save_route_of_every_call():
+    """tests/c/fft_route_check.cpp compiles qo-100-tools_amd/csrc/if_fir_fft_route.h -- the route the launchers and the shim consume --
+    with a plain g++ and checks, for every tap class, decimation 1..64, no bank / slots / own centres, NCO and no_fold on and off, the
+    properties the design states: a named tail, D = F x sub, no NCO form where the tail has none, whole rows behind a decimating
+    tail, two partitions on the 32-row kernel with single-channel tails, the odd kernel exactly where fft_odd_tail holds, and the
+    table image the tail's (cos, tan) trait demands."""
+    import subprocess
+    import tempfile
+    exe = os.path.join(tempfile.mkdtemp(prefix="fft_route_check_"), "fft_route_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "qo-100-tools_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "c", "fft_route_check.cpp"), "-o", exe])
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0 and run.stdout.strip().endswith("routes checked: OK"), run.stdout + run.stderr
+    assert run.stdout.startswith("%d routes" % (14 * 64 * 3 * 2 * 2)), run.stdout
+
+
 def test_no_overlap_save_instantiation_spills():
     """The build records the compiler's per-kernel resource remarks (csrc/if_fir_fft.resources.txt).  No instantiation of
     the overlap-save kernel may use scratch: a spill reload behind row loads in flight waits for all of them (vmcnt is
