@@ -3,13 +3,14 @@ generic kernel, every tap count either side of an overlap class, every L | 64, c
 the history, outputs beyond 2^32 bytes.  Reference as in tests/test_interp_gpu.py: oracle.fir_f64 of the zero-stuffed input
 (complex taps as two real passes), the up-mix in float64 with the integer phase (P n) mod 2^32; SPEC §3 tolerance.
 
-The taps here are not a windowed design (whose end taps are zero, and the next ones 1e-6 of the peak): the first and the last
-tap are the largest of the set, so one tap wrapped into the kept region or one sample missing from the history costs about
-1/sqrt(T) of the output norm."""
+The taps here (tests/matrix_util.py) are not a windowed design (whose end taps are zero, and the next ones 1e-6 of the peak): the
+first and the last tap are the largest of the set, so one tap wrapped into the kept region or one sample missing from the
+history costs about 1/sqrt(T) of the output norm."""
 import numpy as np
 import pytest
 
-TOL = 1e-6
+from matrix_util import TOL, as_c, as_iq, check, edge_taps, signal
+
 OVERLAPS = (256, 512, 1024, 2048, 3072)  # SPEC §6: overlap = the smallest of these that is >= T - 1 (overlap-save: T <= 3073)
 BLOCK = 4096
 BOUNDARY_TAPS = (1, 2, 3, 256, 257, 258, 512, 513, 514, 1024, 1025, 1026, 2048, 2049, 2050, 3072, 3073)
@@ -40,15 +41,6 @@ def zero_stuffed(x, L):
     return u.reshape(-1)
 
 
-def as_c(y):
-    y = np.asarray(y, dtype=np.float64).reshape(-1, 2)
-    return y[:, 0] + 1j * y[:, 1]
-
-
-def as_iq(c):
-    return np.stack([c.real, c.imag], axis=1).reshape(-1)
-
-
 def reference(oracle, taps, x, L, complex_taps=False, word=0, first_out=0):
     """float64: y'[n] = exp(+j 2 pi P n / 2^32) sum_k h[k] u[n-k], n = first_out + output index; x = float32 samples"""
     u = zero_stuffed(x, L)
@@ -62,46 +54,6 @@ def reference(oracle, taps, x, L, complex_taps=False, word=0, first_out=0):
         ph = (n * np.uint64(word)) % np.uint64(1 << 32)
         y = y * np.exp(2j * np.pi * ph.astype(np.float64) / 4294967296.0)
     return as_iq(y)
-
-
-def edge_taps(T, L, complex_taps, seed=0):
-    """seeded normal taps, |h| <= 0.5 inside, the first tap +1 and the last -1 (complex: -j), the whole set scaled to an
-    output level of O(1): sum |h|^2 = L.  float32; complex taps interleaved (re, im)."""
-    rng = np.random.default_rng([T, L, int(complex_taps), seed])
-    h = rng.standard_normal(T).astype(np.float32).astype(np.complex128)
-    if complex_taps:
-        h = h + 1j * rng.standard_normal(T).astype(np.float32)
-    h *= 0.5 / np.max(np.abs(h))
-    h[0] = 1.0
-    if T > 1:
-        h[-1] = -1j if complex_taps else -1.0
-    h *= np.sqrt(L / np.sum(np.abs(h) ** 2))
-    if complex_taps:
-        return as_iq(h).astype(np.float32)
-    return h.real.astype(np.float32)
-
-
-_signals = {}
-
-
-def signal(oracle, n, i16):
-    """(what the library is given, the same samples as float32).  int16: level 14000 with full-scale samples, 32767 and -32768
-    on I and on Q, at the ends, scattered, and in a run"""
-    if (n, i16) not in _signals:
-        x = oracle.synth_iq(n, channel=3)
-        if i16:
-            xi = np.clip(np.round(x * 14000.0), -32768, 32767).astype(np.int16).reshape(-1, 2)
-            full = np.array([[32767, -32768], [-32768, 32767], [32767, 32767], [-32768, -32768]], dtype=np.int16)
-            at = np.unique(np.concatenate([[0, n - 1, n // 3, n // 3 + 1], np.arange(7, n, 97), np.arange(n // 2, min(n, n // 2 + 8))]))
-            at = at[at < n]
-            xi[at] = full[np.arange(at.size) % 4]
-            xi = xi.reshape(-1)
-            _signals[(n, i16)] = (xi, xi.astype(np.float32) * np.float32(2.0 ** -15))
-        else:
-            _signals[(n, i16)] = (x, x)
-        if len(_signals) > 64:
-            _signals.pop(next(iter(_signals)))
-    return _signals[(n, i16)]
 
 
 def make(fir, taps, L, form, ct, n, i16=False, freq=0.0):
@@ -136,12 +88,6 @@ def run_pieces(f, raw, sizes):
     if 2 * pos < raw.size:
         parts.append(f.process(raw[2 * pos:]))
     return np.concatenate(parts)
-
-
-def check(oracle, y, ref, what):
-    l2, mx = oracle.err_metrics(y, ref)
-    print("interp-matrix", what, "l2=%.3g max=%.3g" % (l2, mx))
-    assert l2 <= TOL and mx <= TOL, (what, l2, mx)
 
 
 # ---------------------------------------------------------------- B: every instantiation, every boundary
