@@ -266,6 +266,40 @@ uint8_t if_fir_interp_process(if_fir_interp_t *pCtx, const void *pIQIn, float *p
 uint8_t if_fir_interp_process_device(if_fir_interp_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples,
                                      uint64_t *pullOutSamples);
 
+/* ---- rational resampler (docs/SPEC.md §7; BUILD-DEFINED) -----------------------------------------------------------------
+ * Changes a stream's rate by L/M (L, M in 1..64, used as given: a common factor is legal) in ONE polyphase pass:
+ *     u[n] = x[n/L] if n mod L == 0, else 0;   v[n] = sum_k h[k] u[n-k];   y[m] = v[m*M]
+ * n = index at the L-times rate, m = absolute OUTPUT index, both since init/reset.  A call whose first input has absolute index
+ * c and which brings N inputs emits exactly the outputs m with c*L <= m*M < (c+N)*L: ceil((c+N)*L/M) - ceil(c*L/M) of them,
+ * possibly none when L < M.  process(a||b) == process(a); process(b), bit for bit, wherever the stream is cut.  Taps are used as
+ * given (an image-rejection low-pass needs a gain of L); real or complex, T <= 4096; float32 or int16 input; float32 I/Q output.
+ * No NCO.  Errors: 0 + if_fir_resamp_last_error(); a failed call leaves the context usable and its stream position unchanged.
+ * Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_resamp if_fir_resamp_t;
+
+uint8_t if_fir_resamp_init(if_fir_resamp_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulInterpolation,
+                           uint32_t ulDecimation, uint64_t ullMaxSamples, int32_t lDevice);
+/* complex taps: ulTaps interleaved (re, im) pairs */
+uint8_t if_fir_resamp_init_complex(if_fir_resamp_t **ppCtx, const float *pfTapsIQ, uint32_t ulTaps, uint32_t ulInterpolation,
+                                   uint32_t ulDecimation, uint64_t ullMaxSamples, int32_t lDevice);
+void if_fir_resamp_destroy(if_fir_resamp_t *pCtx);
+/* zero the history and the stream position */
+uint8_t if_fir_resamp_reset(if_fir_resamp_t *pCtx);
+/* IF_FIR_INPUT_F32 or IF_FIR_INPUT_I16 (value = int16 * 2^-15); the history is float32, so a change keeps the stream */
+uint8_t if_fir_resamp_set_input_format(if_fir_resamp_t *pCtx, uint32_t ulFormat);
+uint8_t if_fir_resamp_set_stream(if_fir_resamp_t *pCtx, void *pStream);
+uint8_t if_fir_resamp_synchronize(if_fir_resamp_t *pCtx);
+const char *if_fir_resamp_last_error(const if_fir_resamp_t *pCtx);
+/* outputs of a call with ullSamples inputs at the current stream position */
+uint64_t if_fir_resamp_out_count(const if_fir_resamp_t *pCtx, uint64_t ullSamples);
+/* host pointers, synchronous; ullSamples <= ullMaxSamples of init; pfIQOut holds if_fir_resamp_out_count() samples */
+uint8_t if_fir_resamp_process(if_fir_resamp_t *pCtx, const void *pIQIn, float *pfIQOut, uint64_t ullSamples,
+                              uint64_t *pullOutSamples);
+/* device pointers aligned to one sample (input 8 bytes, 4 for int16; output 8 bytes), asynchronous on the context's stream;
+ * pDevOut holds if_fir_resamp_out_count() samples */
+uint8_t if_fir_resamp_process_device(if_fir_resamp_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples,
+                                     uint64_t *pullOutSamples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,9 @@ uint32_t if_fir_debug_interp_tables(const float *pfTaps, uint32_t ulTaps, uint32
  * the overlap-save backend serves the pair; 0 = taps or interpolation outside if_fir_interp_init's range */
 uint8_t if_fir_debug_interp_plan(uint32_t ulTaps, uint32_t ulInterpolation, uint32_t *pulRows, uint32_t *pulHistLen,
                                  uint32_t *pbFftOk);
+/* resampler (if_fir_resamp_t): ulGridLimit = at most this many workgroups (0 = the launcher's choice; same results: one
+ * workgroup then walks many tiles at test size); *pulTileOutputs (may be NULL) receives the outputs of one tile of this context */
+uint8_t if_fir_debug_resamp_config(if_fir_resamp_t *pCtx, uint32_t ulGridLimit, uint32_t *pulTileOutputs);
 
 #ifdef __cplusplus
 }

@@ -33,12 +33,16 @@ EXPORTS = [
     "if_fir_interp_get_backend", "if_fir_interp_set_input_format", "if_fir_interp_set_nco", "if_fir_interp_get_nco",
     "if_fir_interp_set_stream", "if_fir_interp_synchronize", "if_fir_interp_last_error", "if_fir_interp_out_count",
     "if_fir_interp_process", "if_fir_interp_process_device",
+    "if_fir_resamp_init", "if_fir_resamp_init_complex", "if_fir_resamp_destroy", "if_fir_resamp_reset", "if_fir_resamp_set_input_format",
+    "if_fir_resamp_set_stream", "if_fir_resamp_synchronize", "if_fir_resamp_last_error", "if_fir_resamp_out_count",
+    "if_fir_resamp_process", "if_fir_resamp_process_device",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
                "if_fir_debug_bank_plan", "if_fir_debug_bank_tail", "if_fir_debug_fft_schedule",
                "if_fir_mc_debug_plan", "if_fir_debug_queue_faults",
-               "if_fir_debug_interp_config", "if_fir_debug_interp_seek", "if_fir_debug_interp_tables", "if_fir_debug_interp_plan"]
+               "if_fir_debug_interp_config", "if_fir_debug_interp_seek", "if_fir_debug_interp_tables", "if_fir_debug_interp_plan",
+               "if_fir_debug_resamp_config"]
 MC_ID_BYTES = 128
 
 
@@ -179,7 +183,30 @@ def _load(path, dev):
     L.if_fir_interp_process.restype = u8
     L.if_fir_interp_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.if_fir_interp_process_device.restype = u8
+    L.if_fir_resamp_init.argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u32, u64, i32]
+    L.if_fir_resamp_init.restype = u8
+    L.if_fir_resamp_init_complex.argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u32, u64, i32]
+    L.if_fir_resamp_init_complex.restype = u8
+    L.if_fir_resamp_destroy.argtypes = [vp]
+    L.if_fir_resamp_destroy.restype = None
+    for name in ("reset", "synchronize"):
+        getattr(L, "if_fir_resamp_" + name).argtypes = [vp]
+        getattr(L, "if_fir_resamp_" + name).restype = u8
+    L.if_fir_resamp_set_input_format.argtypes = [vp, u32]
+    L.if_fir_resamp_set_input_format.restype = u8
+    L.if_fir_resamp_set_stream.argtypes = [vp, vp]
+    L.if_fir_resamp_set_stream.restype = u8
+    L.if_fir_resamp_last_error.argtypes = [vp]
+    L.if_fir_resamp_last_error.restype = ctypes.c_char_p
+    L.if_fir_resamp_out_count.argtypes = [vp, u64]
+    L.if_fir_resamp_out_count.restype = u64
+    L.if_fir_resamp_process.argtypes = [vp, vp, f32p, u64, ctypes.POINTER(u64)]
+    L.if_fir_resamp_process.restype = u8
+    L.if_fir_resamp_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.if_fir_resamp_process_device.restype = u8
     if dev:
+        L.if_fir_debug_resamp_config.argtypes = [vp, u32, ctypes.POINTER(u32)]
+        L.if_fir_debug_resamp_config.restype = u8
         L.if_fir_debug_interp_config.argtypes = [vp, u32, u32]
         L.if_fir_debug_interp_config.restype = u8
         L.if_fir_debug_interp_seek.argtypes = [vp, u64]
@@ -562,6 +589,107 @@ def debug_interp_plan(taps, interpolation):
         raise IfFirError("if_fir_debug_interp_plan: %d taps, interpolation %d are outside if_fir_interp_init's range"
                          % (int(taps), int(interpolation)))
     return int(rows.value), int(hist.value), bool(ok.value)
+
+
+class IfFirResamp:
+    """One if_fir_resamp_t: change the rate by interpolation / decimation in one polyphase pass (docs/SPEC.md §7).  Methods
+    mirror the C entry points; how many outputs a call emits depends on the stream position (out_count)."""
+
+    def __init__(self, taps, interpolation, decimation, max_samples=1 << 20, device=0, complex_taps=False, dev=False):
+        self._L = dev_lib() if dev else lib()
+        taps = np.asarray(taps)
+        if np.iscomplexobj(taps):
+            taps = np.ascontiguousarray(taps.astype(np.complex64)).view(np.float32)
+            complex_taps = True
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        self._ctx = ctypes.c_void_p()
+        self.taps = taps
+        self.interpolation, self.decimation = int(interpolation), int(decimation)
+        self._i16 = False
+        self._dev, self._grid_limit = bool(dev), 0
+        init = self._L.if_fir_resamp_init_complex if complex_taps else self._L.if_fir_resamp_init
+        if not init(ctypes.byref(self._ctx), _f32p(taps), taps.size // 2 if complex_taps else taps.size, self.interpolation,
+                    self.decimation, int(max_samples), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._L.if_fir_resamp_last_error(None).decode())
+
+    def _check(self, ok):
+        if not ok:
+            raise IfFirError(self._L.if_fir_resamp_last_error(self._ctx).decode())
+
+    def close(self):
+        if self._ctx:
+            self._L.if_fir_resamp_destroy(self._ctx)
+            self._ctx = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        self._check(self._L.if_fir_resamp_reset(self._ctx))
+
+    def set_input_format(self, fmt):
+        self._check(self._L.if_fir_resamp_set_input_format(self._ctx, int(fmt)))
+        self._i16 = (int(fmt) == INPUT_I16)
+
+    def set_stream(self, stream_handle):
+        self._check(self._L.if_fir_resamp_set_stream(self._ctx, ctypes.c_void_p(stream_handle or None)))
+
+    def synchronize(self):
+        self._check(self._L.if_fir_resamp_synchronize(self._ctx))
+
+    def out_count(self, samples):
+        """if_fir_resamp_out_count(): outputs of a call with `samples` inputs at the current stream position."""
+        return int(self._L.if_fir_resamp_out_count(self._ctx, int(samples)))
+
+    def process(self, iq):
+        """if_fir_resamp_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in,
+        interleaved float32 out."""
+        iq = np.asarray(iq)
+        if self._i16:
+            iq = np.ascontiguousarray(iq, dtype=np.int16).reshape(-1)
+        else:
+            if np.iscomplexobj(iq):
+                iq = np.ascontiguousarray(iq.astype(np.complex64)).view(np.float32)
+            iq = np.ascontiguousarray(iq, dtype=np.float32).reshape(-1)
+        n = iq.size // 2
+        out = np.empty(2 * self.out_count(n), dtype=np.float32)
+        m = ctypes.c_uint64(0)
+        dummy = np.zeros(2, dtype=np.float32)
+        self._check(self._L.if_fir_resamp_process(self._ctx, ctypes.c_void_p(iq.ctypes.data if n else dummy.ctypes.data),
+                                                  _f32p(out if out.size else dummy), n, ctypes.byref(m)))
+        assert m.value * 2 == out.size
+        return out
+
+    def process_device(self, dev_in, dev_out, samples):
+        """if_fir_resamp_process_device(): raw device pointers (ints), asynchronous.  Returns the output sample count."""
+        m = ctypes.c_uint64(0)
+        self._check(self._L.if_fir_resamp_process_device(self._ctx, ctypes.c_void_p(dev_in), ctypes.c_void_p(dev_out),
+                                                         int(samples), ctypes.byref(m)))
+        return int(m.value)
+
+    def debug_config(self, grid_limit=0):
+        """if_fir_debug_resamp_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
+        launcher's choice).  Returns the outputs of one tile of this context."""
+        if not self._dev:
+            raise IfFirError("if_fir_debug_resamp_config is in the development library only: construct with dev=True")
+        tile = ctypes.c_uint32(0)
+        self._check(self._L.if_fir_debug_resamp_config(self._ctx, int(grid_limit), ctypes.byref(tile)))
+        self._grid_limit = int(grid_limit)
+        return int(tile.value)
+
+    def tile_outputs(self):
+        """outputs one workgroup computes per tile (development library); the grid limit stays as it is"""
+        return self.debug_config(self._grid_limit)
 
 
 FFT_TABLE_FLOATS = 2 * (4096 + 4096 + 256 + 1024 + 1024 + 64 + 256)
