@@ -300,6 +300,51 @@ uint8_t if_fir_resamp_process(if_fir_resamp_t *pCtx, const void *pIQIn, float *p
 uint8_t if_fir_resamp_process_device(if_fir_resamp_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples,
                                      uint64_t *pullOutSamples);
 
+/* ---- streaming power-spectrum estimator (docs/SPEC.md §8; BUILD-DEFINED) ---------------------------------------------------
+ * Averaged periodogram (Welch) of a complex IQ stream with the WB detector's dB-to-code scale: IQ in, frames of uint16 spectrum
+ * bins out, in the layout wb_detect_frames_device() reads.  Segment s covers stream samples [s*H, s*H + N); frame f is made of
+ * segments f*K .. f*K + K - 1:
+ *     S_s[k] = |sum_n w[n] x[s*H + n] e^(-2 pi i k n / N)|^2,   P[k] = (sum_s S_s[k]) / (K * sum_n w[n]^2)
+ *     code   = clamp(rint((10 log10(P / fRefPower) + 3.35) / ((16.7 + 3.35) / 65535)), 0, 65535);   P = 0 gives code 0
+ * Output bin j is FFT bin (lFirstBin + j) mod N, -N/2 <= lFirstBin, lFirstBin + ulBins <= N/2.  A frame's segments are summed in
+ * float32 in chunks of 8 (SPEC §8), so process(a||b) == process(a); process(b), bit for bit in both outputs, wherever the stream
+ * is cut.  A call emits the frames whose last segment it completes.  Errors: 0 + if_fir_psd_last_error(); a failed call leaves
+ * the context usable and its stream position unchanged.  Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_psd if_fir_psd_t;
+
+typedef struct
+{
+    uint32_t ulSize;        /* N: 256, 512, 1024, 2048 or 4096 */
+    uint32_t ulHop;         /* H: 1..N */
+    uint32_t ulSegments;    /* K: segments averaged per frame, 1..65535 */
+    int32_t lFirstBin;      /* first output bin, relative to DC */
+    uint32_t ulBins;        /* output bins, 1..N */
+    float fRefPower;        /* > 0 */
+    uint32_t ulInputFormat; /* IF_FIR_INPUT_F32 or IF_FIR_INPUT_I16 (value = int16 * 2^-15) */
+} if_fir_psd_config_t;
+
+/* pfWindow: N float32 values, or NULL = the periodic Hann window 0.5 - 0.5 cos(2 pi n / N), computed in float64 and rounded once.
+ * ullMaxSamples: the most samples of one call; it sizes the context's work buffer (one float32 per bin and chunk of a call) */
+uint8_t if_fir_psd_init(if_fir_psd_t **ppCtx, const if_fir_psd_config_t *pCfg, const float *pfWindow, uint64_t ullMaxSamples,
+                        int32_t lDevice);
+void if_fir_psd_destroy(if_fir_psd_t *pCtx);
+/* back to stream position 0: no samples and no accumulator carried */
+uint8_t if_fir_psd_reset(if_fir_psd_t *pCtx);
+/* the carried samples are float32, so a change keeps the stream */
+uint8_t if_fir_psd_set_input_format(if_fir_psd_t *pCtx, uint32_t ulFormat);
+uint8_t if_fir_psd_set_stream(if_fir_psd_t *pCtx, void *pStream);
+uint8_t if_fir_psd_synchronize(if_fir_psd_t *pCtx);
+const char *if_fir_psd_last_error(const if_fir_psd_t *pCtx);
+/* frames a call with ullSamples samples would emit at the current stream position */
+uint64_t if_fir_psd_frame_count(const if_fir_psd_t *pCtx, uint64_t ullSamples);
+/* host pointers, synchronous; ullSamples <= ullMaxSamples of init.  pusBins holds if_fir_psd_frame_count() x ulBins codes, pfPower
+ * (may be NULL) as many float32 P; *pulFrames (may be NULL) receives the frames emitted */
+uint8_t if_fir_psd_process(if_fir_psd_t *pCtx, const void *pIQIn, uint64_t ullSamples, uint16_t *pusBins, float *pfPower,
+                           uint32_t *pulFrames);
+/* device pointers aligned to one element (input 8 bytes, 4 for int16), asynchronous on the context's stream */
+uint8_t if_fir_psd_process_device(if_fir_psd_t *pCtx, const void *pDevIn, uint64_t ullSamples, uint16_t *pusDevBins, float *pfDevPower,
+                                  uint32_t *pulFrames);
+
 #ifdef __cplusplus
 }
 #endif

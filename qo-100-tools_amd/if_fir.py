@@ -36,14 +36,22 @@ EXPORTS = [
     "if_fir_resamp_init", "if_fir_resamp_init_complex", "if_fir_resamp_destroy", "if_fir_resamp_reset", "if_fir_resamp_set_input_format",
     "if_fir_resamp_set_stream", "if_fir_resamp_synchronize", "if_fir_resamp_last_error", "if_fir_resamp_out_count",
     "if_fir_resamp_process", "if_fir_resamp_process_device",
+    "if_fir_psd_init", "if_fir_psd_destroy", "if_fir_psd_reset", "if_fir_psd_set_input_format", "if_fir_psd_set_stream",
+    "if_fir_psd_synchronize", "if_fir_psd_last_error", "if_fir_psd_frame_count", "if_fir_psd_process", "if_fir_psd_process_device",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
                "if_fir_debug_bank_plan", "if_fir_debug_bank_tail", "if_fir_debug_fft_schedule",
                "if_fir_mc_debug_plan", "if_fir_debug_queue_faults",
                "if_fir_debug_interp_config", "if_fir_debug_interp_seek", "if_fir_debug_interp_tables", "if_fir_debug_interp_plan",
-               "if_fir_debug_resamp_config"]
+               "if_fir_debug_resamp_config", "if_fir_debug_psd_plan"]
 MC_ID_BYTES = 128
+
+
+class PsdConfig(ctypes.Structure):
+    """if_fir_psd_config_t"""
+    _fields_ = [("ulSize", ctypes.c_uint32), ("ulHop", ctypes.c_uint32), ("ulSegments", ctypes.c_uint32), ("lFirstBin", ctypes.c_int32),
+                ("ulBins", ctypes.c_uint32), ("fRefPower", ctypes.c_float), ("ulInputFormat", ctypes.c_uint32)]
 
 
 class IfFirError(RuntimeError):
@@ -204,7 +212,29 @@ def _load(path, dev):
     L.if_fir_resamp_process.restype = u8
     L.if_fir_resamp_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.if_fir_resamp_process_device.restype = u8
+    u16p = ctypes.POINTER(ctypes.c_uint16)
+    L.if_fir_psd_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(PsdConfig), f32p, u64, i32]
+    L.if_fir_psd_init.restype = u8
+    L.if_fir_psd_destroy.argtypes = [vp]
+    L.if_fir_psd_destroy.restype = None
+    for name in ("reset", "synchronize"):
+        getattr(L, "if_fir_psd_" + name).argtypes = [vp]
+        getattr(L, "if_fir_psd_" + name).restype = u8
+    L.if_fir_psd_set_input_format.argtypes = [vp, u32]
+    L.if_fir_psd_set_input_format.restype = u8
+    L.if_fir_psd_set_stream.argtypes = [vp, vp]
+    L.if_fir_psd_set_stream.restype = u8
+    L.if_fir_psd_last_error.argtypes = [vp]
+    L.if_fir_psd_last_error.restype = ctypes.c_char_p
+    L.if_fir_psd_frame_count.argtypes = [vp, u64]
+    L.if_fir_psd_frame_count.restype = u64
+    L.if_fir_psd_process.argtypes = [vp, vp, u64, u16p, f32p, ctypes.POINTER(u32)]
+    L.if_fir_psd_process.restype = u8
+    L.if_fir_psd_process_device.argtypes = [vp, vp, u64, vp, vp, ctypes.POINTER(u32)]
+    L.if_fir_psd_process_device.restype = u8
     if dev:
+        L.if_fir_debug_psd_plan.argtypes = [vp, u64, ctypes.POINTER(u64)]
+        L.if_fir_debug_psd_plan.restype = u8
         L.if_fir_debug_resamp_config.argtypes = [vp, u32, ctypes.POINTER(u32)]
         L.if_fir_debug_resamp_config.restype = u8
         L.if_fir_debug_interp_config.argtypes = [vp, u32, u32]
@@ -690,6 +720,108 @@ class IfFirResamp:
     def tile_outputs(self):
         """outputs one workgroup computes per tile (development library); the grid limit stays as it is"""
         return self.debug_config(self._grid_limit)
+
+
+class IfFirPsd:
+    """One if_fir_psd_t: averaged periodogram of an IQ stream as frames of uint16 spectrum codes, the layout wb_detect reads
+    (docs/SPEC.md §8).  Methods mirror the C entry points; how many frames a call emits depends on the stream position
+    (frame_count)."""
+
+    def __init__(self, size, hop, segments, first_bin, bins, ref_power=1.0, window=None, input_format=INPUT_F32,
+                 max_samples=1 << 20, device=0, dev=False):
+        self._L = dev_lib() if dev else lib()
+        self._ctx = ctypes.c_void_p()
+        self._dev = bool(dev)
+        self.size, self.hop, self.segments, self.first_bin, self.bins = int(size), int(hop), int(segments), int(first_bin), int(bins)
+        cfg = PsdConfig(self.size, self.hop, self.segments, self.first_bin, self.bins, float(ref_power), int(input_format))
+        self._i16 = (int(input_format) == INPUT_I16)
+        wp = None
+        if window is not None:
+            window = np.ascontiguousarray(window, dtype=np.float32)
+            if window.size != self.size:
+                raise IfFirError("IfFirPsd: the window must have size = %d values (got %d)" % (self.size, window.size))
+            wp = _f32p(window)
+        if not self._L.if_fir_psd_init(ctypes.byref(self._ctx), ctypes.byref(cfg), wp, int(max_samples), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._L.if_fir_psd_last_error(None).decode())
+
+    def _check(self, ok):
+        if not ok:
+            raise IfFirError(self._L.if_fir_psd_last_error(self._ctx).decode())
+
+    def close(self):
+        if self._ctx:
+            self._L.if_fir_psd_destroy(self._ctx)
+            self._ctx = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        self._check(self._L.if_fir_psd_reset(self._ctx))
+
+    def set_input_format(self, fmt):
+        self._check(self._L.if_fir_psd_set_input_format(self._ctx, int(fmt)))
+        self._i16 = (int(fmt) == INPUT_I16)
+
+    def set_stream(self, stream_handle):
+        self._check(self._L.if_fir_psd_set_stream(self._ctx, ctypes.c_void_p(stream_handle or None)))
+
+    def synchronize(self):
+        self._check(self._L.if_fir_psd_synchronize(self._ctx))
+
+    def frame_count(self, samples):
+        """if_fir_psd_frame_count(): frames of a call with `samples` samples at the current stream position."""
+        return int(self._L.if_fir_psd_frame_count(self._ctx, int(samples)))
+
+    def process(self, iq, want_power=True):
+        """if_fir_psd_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in;
+        returns ((frames, bins) uint16 codes, (frames, bins) float32 power or None)."""
+        iq = np.asarray(iq)
+        if self._i16:
+            iq = np.ascontiguousarray(iq, dtype=np.int16).reshape(-1)
+        else:
+            if np.iscomplexobj(iq):
+                iq = np.ascontiguousarray(iq.astype(np.complex64)).view(np.float32)
+            iq = np.ascontiguousarray(iq, dtype=np.float32).reshape(-1)
+        n = iq.size // 2
+        frames = self.frame_count(n)
+        codes = np.empty((frames, self.bins), dtype=np.uint16)
+        power = np.empty((frames, self.bins), dtype=np.float32) if want_power else None
+        m = ctypes.c_uint32(0)
+        dummy = np.zeros(2, dtype=np.float32)
+        self._check(self._L.if_fir_psd_process(
+            self._ctx, ctypes.c_void_p(iq.ctypes.data if n else dummy.ctypes.data), n,
+            codes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)) if frames else None,
+            _f32p(power) if want_power and frames else None, ctypes.byref(m)))
+        assert m.value == frames
+        return codes, power
+
+    def process_device(self, dev_in, samples, dev_bins, dev_power=0):
+        """if_fir_psd_process_device(): raw device pointers (ints; dev_power may be 0), asynchronous.  Returns the frames emitted."""
+        m = ctypes.c_uint32(0)
+        self._check(self._L.if_fir_psd_process_device(self._ctx, ctypes.c_void_p(dev_in or None), int(samples),
+                                                      ctypes.c_void_p(dev_bins or None), ctypes.c_void_p(dev_power or None),
+                                                      ctypes.byref(m)))
+        return int(m.value)
+
+    def debug_plan(self, samples):
+        """if_fir_debug_psd_plan() (development library: construct with dev=True): (segments, chunks, frames, carried samples)
+        of the next call of `samples` samples."""
+        if not self._dev:
+            raise IfFirError("if_fir_debug_psd_plan is in the development library only: construct with dev=True")
+        out = (ctypes.c_uint64 * 4)()
+        self._check(self._L.if_fir_debug_psd_plan(self._ctx, int(samples), out))
+        return tuple(int(v) for v in out)
 
 
 FFT_TABLE_FLOATS = 2 * (4096 + 4096 + 256 + 1024 + 1024 + 64 + 256)

@@ -1,0 +1,151 @@
+"""The power-spectrum estimator's host side (no GPU): its C ABI in the header, the libraries and the binding; the call planning
+of qo-100-tools_amd/csrc/if_fir_psd_plan.h through the stand-alone checker tests/c/psd_plan_check.cpp (built with the address
+and undefined-behaviour sanitizers); the float64 reference of tests/psd_ref.py against scipy.signal.welch; the code mapping at
+its clamps and ties; the tolerance of the GPU test from a plain complex64 implementation; the compiled kernels' resources."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import psd_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "qo-100-tools_amd", "csrc")
+PSD_ABI = {"if_fir_psd_init", "if_fir_psd_destroy", "if_fir_psd_reset", "if_fir_psd_set_input_format", "if_fir_psd_set_stream",
+           "if_fir_psd_synchronize", "if_fir_psd_last_error", "if_fir_psd_frame_count", "if_fir_psd_process",
+           "if_fir_psd_process_device"}
+PSD_DEV = {"if_fir_debug_psd_plan"}
+
+
+def _defined(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True).stdout
+    return {line.split()[-1] for line in out.splitlines() if line.strip()}
+
+
+def test_header_declares_and_libraries_export_the_estimator(fir):
+    header = open(os.path.join(ROOT, "include", "if_fir.h")).read()
+    declared = set(re.findall(r"\b(if_fir_psd_[a-z_]+)\s*\(", header))
+    assert declared == PSD_ABI, declared ^ PSD_ABI
+    assert "typedef struct if_fir_psd if_fir_psd_t;" in header and "} if_fir_psd_config_t;" in header
+    assert PSD_ABI <= set(fir.EXPORTS) and PSD_DEV <= set(fir.DEV_EXPORTS)
+    dbg = open(os.path.join(ROOT, "include", "if_fir_debug.h")).read()
+    assert PSD_DEV <= set(re.findall(r"^\w+ \*?(if_fir_[a-z_]+)\s*\(", dbg, re.M))
+    fir.lib()
+    product, dev = _defined(fir.LIB_PATH), _defined(fir.DEV_LIB_PATH)
+    assert PSD_ABI <= product and PSD_ABI <= dev
+    assert not (PSD_DEV & product) and PSD_DEV <= dev
+    for name in ("process", "process_device", "frame_count", "reset", "set_input_format", "set_stream", "__enter__", "__exit__"):
+        assert hasattr(fir.IfFirPsd, name), name
+    # the binding's structure is the header's: seven 4-byte fields in this order
+    fields = re.search(r"typedef struct\s*\{(.*?)\}\s*if_fir_psd_config_t;", header, re.S).group(1)
+    names = re.findall(r"^\s*(?:uint32_t|int32_t|float)\s+(\w+);", fields, re.M)
+    assert names == [f[0] for f in fir.PsdConfig._fields_] and len(names) == 7
+
+
+def test_c_selftest_compiles_as_c99(tmp_path):
+    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"), "-c",
+                           os.path.join(ROOT, "tests", "c", "if_fir_psd_selftest.c"), "-o", str(tmp_path / "selftest.o")])
+
+
+def test_plan_of_every_size_hop_and_stream_position(tmp_path):
+    """tests/c/psd_plan_check.cpp with -fsanitize=address,undefined: every N, H in {1, 3, N/4, N/2, N-1, N}, K in {1, 3, 8, 9, 20,
+    65535}, call lengths around every segment, chunk and frame boundary, positions 0 and around 2^32 (the checker's header
+    comment lists the properties)"""
+    exe = str(tmp_path / "psd_plan_check")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-I" + CSRC, os.path.join(ROOT, "tests", "c", "psd_plan_check.cpp"), "-o", exe])
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0 and run.stdout.strip().endswith("calls checked: OK"), run.stdout + run.stderr
+    configs = 5 * 6 * 6 * 2   # position 0, and the state built past 2^32
+    assert int(run.stdout.split()[0]) >= configs, run.stdout
+
+
+def test_reference_plan_counts():
+    """psd_ref.plan (a walk) and psd_ref.frame_count (closed form) agree however a stream is cut"""
+    rng = np.random.default_rng(8)
+    for N, H, K in ((256, 1, 20), (1024, 385, 9), (256, 256, 1), (512, 192, 3)):
+        pos = carried = frames = 0
+        for n in [0, 1, N - 2, 1, 1, H, 7 * H, 8 * H + 3] + list(rng.integers(0, 12 * H + N, 40)):
+            segs, chunks, f, carry = psd_ref.plan(pos, carried, int(n), N, H, K)
+            assert f == psd_ref.frame_count(pos, int(n), N, H, K) and carry < 7 * H + N
+            pos, carried, frames = pos + int(n), carry, frames + f
+        assert frames == psd_ref.segments_complete(pos, N, H) // K
+
+
+@pytest.mark.parametrize("N,H,window", [(256, 96, "hann"), (1024, 1024, "asymmetric")])
+def test_reference_is_welch(N, H, window):
+    """one frame with K = all segments equals scipy.signal.welch (two-sided density, fs = 1, no detrending, mean) at 1e-12"""
+    import scipy.signal
+    rng = np.random.default_rng(N)
+    K = 11
+    n = (K - 1) * H + N
+    x = rng.standard_normal(2 * n).astype(np.float32)
+    w = psd_ref.hann(N) if window == "hann" else psd_ref.asymmetric_window(N)
+    got = psd_ref.power_f64(x, N, H, K, w, -N // 2, N)
+    assert got.shape == (1, N)
+    _, want = scipy.signal.welch(psd_ref.as_c(x), fs=1.0, window=w.astype(np.float64), nperseg=N, noverlap=N - H, nfft=N,
+                                 detrend=False, return_onesided=False, scaling="density", average="mean")
+    want = np.fft.fftshift(want)   # welch: FFT order; ours: from -N/2
+    assert np.max(np.abs(got[0] - want)) <= 1e-12 * np.max(want)
+    # white noise of variance sigma^2 per complex sample gives P ~ sigma^2 (here 2: unit variance on I and on Q)
+    assert abs(np.mean(got) - 2.0) < 0.2
+    # a sub-span is the same values
+    sub = psd_ref.power_f64(x, N, H, K, w, -5, 9)
+    assert np.array_equal(sub[0], got[0][N // 2 - 5:N // 2 + 4])
+
+
+def test_code_mapping_clamps_and_ties():
+    step = psd_ref.SLOPE
+    db = lambda c: psd_ref.ZERO_DB + c * step
+    p = lambda c: 10.0 ** (db(c) / 10.0)
+    assert np.array_equal(psd_ref.codes([0.0, p(-5.0), p(0.0), p(65535.0), p(70000.0), 1e30], 1.0), [0, 0, 0, 65535, 65535, 65535])
+    assert np.array_equal(psd_ref.codes(np.array([p(100.0), p(16500.0)]) * 3.0, 3.0), [100, 16500])
+    # exact half-code points through the reference's own dB -> code step: ties go to the even code.  A tie is a dB value whose
+    # position on the scale, (dB - zero) / slope in float64, is exactly c + 0.5; it is looked for among the neighbours of
+    # zero + (c + 0.5) slope, and enough of them exist
+    ties = {}
+    for c in range(0, 65535, 97):
+        db0 = np.float64(psd_ref.ZERO_DB + (c + 0.5) * step)
+        for cand in (db0, np.nextafter(db0, np.inf), np.nextafter(db0, -np.inf)):
+            if (cand - psd_ref.ZERO_DB) / step == c + 0.5:
+                ties[c] = cand
+                break
+    assert sum(c % 2 == 0 for c in ties) >= 20 and sum(c % 2 == 1 for c in ties) >= 20, len(ties)
+    for c, tie in ties.items():
+        assert int(psd_ref.code_of_db(tie)) == (c if c % 2 == 0 else c + 1), (c, tie)     # half up would give c + 1 always
+    assert int(psd_ref.code_of_db(-np.inf)) == 0 and int(psd_ref.code_of_db(np.inf)) == 65535
+    # around a tie, through the whole mapping from power
+    for c in (10.5, 11.5, 40000.5):
+        assert list(psd_ref.codes([p(c - 1e-6), p(c + 1e-6)], 1.0)) == [int(np.floor(c)), int(np.floor(c)) + 1]
+
+
+def test_tolerance_is_four_times_a_complex64_implementation(oracle):
+    """SPEC §8: the GPU test's bound is 4 x the worst error of a plain complex64 implementation (scipy.fft on complex64, float32
+    sums in the §8 order) against the float64 reference over the GPU test's matrix, and never above 1e-5"""
+    worst = 0.0
+    for N, H in psd_ref.MATRIX:
+        for K in psd_ref.SEGMENTS:
+            base = oracle.synth_iq(psd_ref.matrix_samples(N, H, K), channel=3)
+            for i16 in (False, True):
+                _, x = psd_ref.matrix_signal(base, N, i16)
+                for w in (None, psd_ref.asymmetric_window(N)):
+                    ref = psd_ref.power_f64(x, N, H, K, w)
+                    got = psd_ref.power_c64(x, N, H, K, w)
+                    assert ref.shape[0] >= 2
+                    worst = max(worst, float(np.max(np.max(np.abs(got - ref), axis=1) / np.max(ref, axis=1))))
+    print("complex64 worst error %.4g, EPS %.4g" % (worst, psd_ref.EPS))
+    assert worst == pytest.approx(psd_ref.C64_WORST, rel=0.02)
+    assert psd_ref.EPS == 4 * psd_ref.C64_WORST and psd_ref.EPS <= 1e-5
+
+
+def test_psd_kernels_use_no_scratch():
+    path = os.path.join(CSRC, "if_fir_psd.resources.txt")
+    assert os.path.exists(path), "build() first: the Makefile writes this file next to if_fir_psd.o"
+    text = open(path).read()
+    names = re.findall(r"Function Name: (\S+)", text)
+    # chunk kernel: 5 sizes x (float32, int16); carry copy: 2; frame kernel: 1
+    assert len(names) == 13 and sum("psd_chunk_kernel" in n for n in names) == 10, names
+    assert re.findall(r"VGPRs Spill: (\d+)", text) == ["0"] * 13
+    assert re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", text) == ["0"] * 13
