@@ -4,8 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -16,75 +14,45 @@
 #include "if_fir_debug.h"
 #endif
 #include "if_fir_psd.h"
+#include "if_fir_stream_ctx.h"
 
 #define IF_FIR_API extern "C" __attribute__((visibility("default")))
 
-struct if_fir_psd
+// the streaming state: what a call advances (and a failed if_fir_psd_process puts back)
+struct psd_state
 {
-    int device;
-    hipStream_t own_stream;
-    hipStream_t stream;
+    int carry_cur, acc_cur;   // which of d_carry / d_acc the next call reads
+    uint64_t position;        // samples since init/reset
+    uint64_t carried;         // samples in d_carry[carry_cur]
+};
+
+struct if_fir_psd : if_fir::StreamCtx
+{
     int N, H, K, bins;
-    int in_i16;
     float scale;              // 1 / (K sum w^2), rounded once
     double ref_power;
     float *d_window;
     float2 *d_twiddle;
     uint16_t *d_bin_pos;
     float2 *d_carry[2];       // the samples of the open chunk, float32, ping-pong
-    int carry_cur;
     float *d_acc[2];          // the open frame's accumulator, ping-pong
-    int acc_cur;
     float *d_work;            // chunk sums of one call
     uint64_t work_chunks;
-    uint64_t position;        // samples since init/reset
-    uint64_t carried;         // samples in d_carry[carry_cur]
-    uint64_t max_samples;
+    psd_state st;
     void *d_stage_in;         // if_fir_psd_process: staging, allocated by its first call (device-pointer users never pay for it)
     uint16_t *d_stage_codes;
     float *d_stage_power;
-    mutable char err[256];
 };
 
+using if_fir::set_err;
 static thread_local char g_psd_init_err[256] = "";
-
-static void set_err(const if_fir_psd *ctx, const char *fmt, ...)
-{
-    char *dst = ctx ? ctx->err : g_psd_init_err;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(dst, 256, fmt, ap);
-    va_end(ap);
-}
-
-#define HIP_TRY(ctx, call)                                                                                \
-    do                                                                                                    \
-    {                                                                                                     \
-        hipError_t e_ = (call);                                                                           \
-        if (e_ != hipSuccess)                                                                             \
-        {                                                                                                 \
-            set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);      \
-            return 0;                                                                                     \
-        }                                                                                                 \
-    } while (0)
 
 static void free_ctx(if_fir_psd *c)
 {
     if (!c)
         return;
-    (void)hipSetDevice(c->device);
-    if (c->stream && c->stream != c->own_stream && hipStreamSynchronize(c->stream) != hipSuccess)
-        (void)hipGetLastError();
-    if (c->own_stream)
-    {
-        (void)hipStreamSynchronize(c->own_stream);
-        (void)hipStreamDestroy(c->own_stream);
-    }
-    void *bufs[] = {c->d_window, c->d_twiddle, c->d_bin_pos, c->d_carry[0], c->d_carry[1], c->d_acc[0], c->d_acc[1],
-                    c->d_work, c->d_stage_in, c->d_stage_codes, c->d_stage_power};
-    for (void *b : bufs)
-        if (b)
-            (void)hipFree(b);
+    if_fir::stream_ctx_close(c, {c->d_window, c->d_twiddle, c->d_bin_pos, c->d_carry[0], c->d_carry[1], c->d_acc[0], c->d_acc[1], c->d_work,
+                                 c->d_stage_in, c->d_stage_codes, c->d_stage_power});
     delete c;
 }
 
@@ -93,64 +61,64 @@ IF_FIR_API uint8_t if_fir_psd_init(if_fir_psd_t **ppCtx, const if_fir_psd_config
 {
     if (!ppCtx)
     {
-        set_err(nullptr, "if_fir_psd_init: ppCtx is NULL");
+        set_err(g_psd_init_err, "if_fir_psd_init: ppCtx is NULL");
         return 0;
     }
     *ppCtx = nullptr;
     if (!pCfg)
     {
-        set_err(nullptr, "if_fir_psd_init: pCfg is NULL");
+        set_err(g_psd_init_err, "if_fir_psd_init: pCfg is NULL");
         return 0;
     }
     const uint32_t N = pCfg->ulSize;
     if (!if_fir::psd_size_ok(N))
     {
-        set_err(nullptr, "if_fir_psd_init: transform size must be 256, 512, 1024, 2048 or 4096 (got %u)", N);
+        set_err(g_psd_init_err, "if_fir_psd_init: transform size must be 256, 512, 1024, 2048 or 4096 (got %u)", N);
         return 0;
     }
     if (pCfg->ulHop < 1 || pCfg->ulHop > N)
     {
-        set_err(nullptr, "if_fir_psd_init: hop must be 1..%u (got %u)", N, pCfg->ulHop);
+        set_err(g_psd_init_err, "if_fir_psd_init: hop must be 1..%u (got %u)", N, pCfg->ulHop);
         return 0;
     }
     if (pCfg->ulSegments < 1 || pCfg->ulSegments > if_fir::PSD_MAX_SEGMENTS)
     {
-        set_err(nullptr, "if_fir_psd_init: segments per frame must be 1..%u (got %u)", if_fir::PSD_MAX_SEGMENTS, pCfg->ulSegments);
+        set_err(g_psd_init_err, "if_fir_psd_init: segments per frame must be 1..%u (got %u)", if_fir::PSD_MAX_SEGMENTS, pCfg->ulSegments);
         return 0;
     }
     const int64_t half = (int64_t)N / 2, first = pCfg->lFirstBin;
     if (pCfg->ulBins < 1 || pCfg->ulBins > N || first < -half || first + (int64_t)pCfg->ulBins > half)
     {
-        set_err(nullptr, "if_fir_psd_init: bins [%d, %lld) are outside [-%lld, %lld) (ulBins 1..%u)", pCfg->lFirstBin,
+        set_err(g_psd_init_err, "if_fir_psd_init: bins [%d, %lld) are outside [-%lld, %lld) (ulBins 1..%u)", pCfg->lFirstBin,
                 (long long)(first + (int64_t)pCfg->ulBins), (long long)half, (long long)half, N);
         return 0;
     }
     if (!(pCfg->fRefPower > 0.0f) || !std::isfinite(pCfg->fRefPower))
     {
-        set_err(nullptr, "if_fir_psd_init: fRefPower must be a finite value > 0");
+        set_err(g_psd_init_err, "if_fir_psd_init: fRefPower must be a finite value > 0");
         return 0;
     }
     if (pCfg->ulInputFormat > IF_FIR_INPUT_I16)
     {
-        set_err(nullptr, "if_fir_psd_init: unknown input format %u", pCfg->ulInputFormat);
+        set_err(g_psd_init_err, "if_fir_psd_init: unknown input format %u", pCfg->ulInputFormat);
         return 0;
     }
     if (ullMaxSamples == 0 || ullMaxSamples > ((uint64_t)1 << 40))
     {
-        set_err(nullptr, "if_fir_psd_init: ullMaxSamples must be 1..2^40 (got %llu)", (unsigned long long)ullMaxSamples);
+        set_err(g_psd_init_err, "if_fir_psd_init: ullMaxSamples must be 1..2^40 (got %llu)", (unsigned long long)ullMaxSamples);
         return 0;
     }
     const uint32_t H = pCfg->ulHop, K = pCfg->ulSegments, bins = pCfg->ulBins;
     const uint64_t work_chunks = if_fir::psd_max_chunks(ullMaxSamples, H, K);
     if (if_fir::psd_max_segments(ullMaxSamples, H) >= if_fir::PSD_MAX_CALL_SEGMENTS)
     {
-        set_err(nullptr, "if_fir_psd_init: a call of ullMaxSamples = %llu samples at hop %u could sum 2^31 segments or more: lower "
+        set_err(g_psd_init_err, "if_fir_psd_init: a call of ullMaxSamples = %llu samples at hop %u could sum 2^31 segments or more: lower "
                          "ullMaxSamples", (unsigned long long)ullMaxSamples, H);
         return 0;
     }
     if (work_chunks * bins > ((uint64_t)1 << 29))
     {
-        set_err(nullptr, "if_fir_psd_init: a call of ullMaxSamples = %llu samples at hop %u would need %llu chunk sums of %u bins; "
+        set_err(g_psd_init_err, "if_fir_psd_init: a call of ullMaxSamples = %llu samples at hop %u would need %llu chunk sums of %u bins; "
                          "the work buffer is limited to 2^29 values: lower ullMaxSamples",
                 (unsigned long long)ullMaxSamples, H, (unsigned long long)work_chunks, bins);
         return 0;
@@ -163,14 +131,14 @@ IF_FIR_API uint8_t if_fir_psd_init(if_fir_psd_t **ppCtx, const if_fir_psd_config
         window[i] = pfWindow ? pfWindow[i] : (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)N));
         if (!std::isfinite(window[i]))
         {
-            set_err(nullptr, "if_fir_psd_init: window value %u is not finite", i);
+            set_err(g_psd_init_err, "if_fir_psd_init: window value %u is not finite", i);
             return 0;
         }
         energy += (double)window[i] * (double)window[i];
     }
     if (!(energy > 0.0))
     {
-        set_err(nullptr, "if_fir_psd_init: the window is all zero");
+        set_err(g_psd_init_err, "if_fir_psd_init: the window is all zero");
         return 0;
     }
     std::vector<float> twiddle(2 * (size_t)N);
@@ -184,25 +152,14 @@ IF_FIR_API uint8_t if_fir_psd_init(if_fir_psd_t **ppCtx, const if_fir_psd_config
     for (uint32_t j = 0; j < bins; j++)
         where[j] = (uint16_t)if_fir::psd_bin_position((uint32_t)((first + (int64_t)j + (int64_t)N) % (int64_t)N), N);
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    {
-        (void)hipGetLastError();
-        set_err(nullptr, "if_fir_psd_init: no HIP device");
+    if (!if_fir::stream_ctx_device_ok(g_psd_init_err, "if_fir_psd_init", lDevice))
         return 0;
-    }
-    if (lDevice < 0 || lDevice >= ndev)
-    {
-        set_err(nullptr, "if_fir_psd_init: device %d does not exist (%d visible)", lDevice, ndev);
-        return 0;
-    }
     if_fir_psd *c = new (std::nothrow) if_fir_psd();
     if (!c)
     {
-        set_err(nullptr, "if_fir_psd_init: out of host memory");
+        set_err(g_psd_init_err, "if_fir_psd_init: out of host memory");
         return 0;
     }
-    c->device = lDevice;
     c->N = (int)N;
     c->H = (int)H;
     c->K = (int)K;
@@ -210,40 +167,22 @@ IF_FIR_API uint8_t if_fir_psd_init(if_fir_psd_t **ppCtx, const if_fir_psd_config
     c->in_i16 = (int)pCfg->ulInputFormat;
     c->ref_power = (double)pCfg->fRefPower;
     c->scale = (float)(1.0 / ((double)K * energy));
-    c->max_samples = ullMaxSamples;
     c->work_chunks = work_chunks;
     const size_t carry_bytes = ((size_t)(if_fir::PSD_CHUNK - 1) * H + N) * sizeof(float2);
-    hipError_t e = hipSetDevice(lDevice);
-    if (e == hipSuccess)
-        e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
-    c->stream = c->own_stream;
-    if (e == hipSuccess)
-        e = hipMalloc(&c->d_window, N * sizeof(float));
-    if (e == hipSuccess)
-        e = hipMemcpy(c->d_window, window.data(), N * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMalloc(&c->d_twiddle, N * sizeof(float2));
-    if (e == hipSuccess)
-        e = hipMemcpy(c->d_twiddle, twiddle.data(), N * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMalloc(&c->d_bin_pos, bins * sizeof(uint16_t));
-    if (e == hipSuccess)
-        e = hipMemcpy(c->d_bin_pos, where.data(), bins * sizeof(uint16_t), hipMemcpyHostToDevice);
-    for (int i = 0; i < 2 && e == hipSuccess; i++)
+    hipError_t e = if_fir::stream_ctx_open(c, lDevice, ullMaxSamples);
+    if_fir::stream_ctx_alloc_upload(e, &c->d_window, window.data(), N * sizeof(float));
+    if_fir::stream_ctx_alloc_upload(e, &c->d_twiddle, twiddle.data(), N * sizeof(float2));
+    if_fir::stream_ctx_alloc_upload(e, &c->d_bin_pos, where.data(), bins * sizeof(uint16_t));
+    for (int i = 0; i < 2; i++)
     {
-        e = hipMalloc(&c->d_carry[i], carry_bytes);
-        if (e == hipSuccess)
-            e = hipMemset(c->d_carry[i], 0, carry_bytes);
-        if (e == hipSuccess)
-            e = hipMalloc(&c->d_acc[i], bins * sizeof(float));
-        if (e == hipSuccess)
-            e = hipMemset(c->d_acc[i], 0, bins * sizeof(float));
+        if_fir::stream_ctx_alloc_zeroed(e, &c->d_carry[i], carry_bytes);
+        if_fir::stream_ctx_alloc_zeroed(e, &c->d_acc[i], bins * sizeof(float));
     }
     if (e == hipSuccess)
         e = hipMalloc(&c->d_work, (size_t)work_chunks * bins * sizeof(float));
     if (e != hipSuccess)
     {
-        set_err(nullptr, "if_fir_psd_init: %s", hipGetErrorString(e));
+        set_err(g_psd_init_err, "if_fir_psd_init: %s", hipGetErrorString(e));
         (void)hipGetLastError();
         free_ctx(c);
         return 0;
@@ -269,45 +208,30 @@ IF_FIR_API uint8_t if_fir_psd_reset(if_fir_psd_t *pCtx)
     HIP_TRY(pCtx, hipSetDevice(pCtx->device));
     HIP_TRY(pCtx, hipStreamSynchronize(pCtx->stream));
     // (no buffer needs zeroing: nothing is read of the carried samples or the accumulator beyond what the position says is there)
-    pCtx->position = 0;
-    pCtx->carried = 0;
+    pCtx->st.position = 0;
+    pCtx->st.carried = 0;
     return 1;
 }
 
 IF_FIR_API uint8_t if_fir_psd_set_input_format(if_fir_psd_t *pCtx, uint32_t ulFormat)
 {
-    if (!pCtx)
-        return 0;
-    if (ulFormat > IF_FIR_INPUT_I16)
-    {
-        set_err(pCtx, "if_fir_psd_set_input_format: unknown format %u", ulFormat);
-        return 0;
-    }
-    pCtx->in_i16 = (int)ulFormat; // (the carried samples are kept as float32: a change of format keeps the stream)
-    return 1;
+    return if_fir::stream_ctx_set_input_format(pCtx, "if_fir_psd_set_input_format", ulFormat);
 }
 
 IF_FIR_API uint8_t if_fir_psd_set_stream(if_fir_psd_t *pCtx, void *pStream)
 {
-    if (!pCtx)
-        return 0;
-    pCtx->stream = pStream ? static_cast<hipStream_t>(pStream) : pCtx->own_stream;
-    return 1;
+    return if_fir::stream_ctx_set_stream(pCtx, pStream);
 }
 
 IF_FIR_API uint8_t if_fir_psd_synchronize(if_fir_psd_t *pCtx)
 {
-    if (!pCtx)
-        return 0;
-    HIP_TRY(pCtx, hipSetDevice(pCtx->device));
-    HIP_TRY(pCtx, hipStreamSynchronize(pCtx->stream));
-    return 1;
+    return if_fir::stream_ctx_synchronize(pCtx);
 }
 
 IF_FIR_API uint64_t if_fir_psd_frame_count(const if_fir_psd_t *pCtx, uint64_t ullSamples)
 {
     if_fir::PsdPlan plan;
-    if (!pCtx || !if_fir::psd_plan(pCtx->position, pCtx->carried, ullSamples, (uint32_t)pCtx->N, (uint32_t)pCtx->H, (uint32_t)pCtx->K, &plan))
+    if (!pCtx || !if_fir::psd_plan(pCtx->st.position, pCtx->st.carried, ullSamples, (uint32_t)pCtx->N, (uint32_t)pCtx->H, (uint32_t)pCtx->K, &plan))
         return 0;
     return plan.frames;
 }
@@ -315,36 +239,28 @@ IF_FIR_API uint64_t if_fir_psd_frame_count(const if_fir_psd_t *pCtx, uint64_t ul
 static uint8_t run_device(if_fir_psd *c, const void *in, uint16_t *codes, float *power, uint64_t n, uint32_t *pframes, const char *who)
 {
     if_fir::PsdPlan plan;
-    if (n > c->max_samples)
-    {
-        set_err(c, "%s: %llu samples exceed ullMaxSamples %llu of init", who, (unsigned long long)n, (unsigned long long)c->max_samples);
+    if (!if_fir::stream_ctx_fits(c, who, n))
         return 0;
-    }
-    if (!if_fir::psd_plan(c->position, c->carried, n, (uint32_t)c->N, (uint32_t)c->H, (uint32_t)c->K, &plan) ||
+    if (!if_fir::psd_plan(c->st.position, c->st.carried, n, (uint32_t)c->N, (uint32_t)c->H, (uint32_t)c->K, &plan) ||
         plan.chunks > c->work_chunks || plan.frames > 0xffffffffull)
     {
-        set_err(c, "%s: sample count too large", who);
+        set_err(c->err, "%s: sample count too large", who);
         return 0;
     }
     const uintptr_t in_mask = c->in_i16 ? 3 : 7;
     if (((uintptr_t)in & in_mask) || ((uintptr_t)codes & 1) || ((uintptr_t)power & 3))
     {
-        set_err(c, "%s: device pointers must be aligned to one element: %u-byte (input), 2-byte (codes), 4-byte (power)", who,
+        set_err(c->err, "%s: device pointers must be aligned to one element: %u-byte (input), 2-byte (codes), 4-byte (power)", who,
                 (unsigned)in_mask + 1);
         return 0;
     }
     if ((n && !in) || (plan.frames && !codes))
     {
-        set_err(c, "%s: NULL device pointer", who);
+        set_err(c->err, "%s: NULL device pointer", who);
         return 0;
     }
-    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(c->stream, &capture) == hipSuccess && capture != hipStreamCaptureStatusNone)
-    {
-        set_err(c, "%s: the context's stream is being captured into a hipGraph; calls carry host-side streaming state and "
-                   "cannot be replayed", who);
+    if (if_fir::stream_ctx_capturing(c, who))
         return 0;
-    }
     if (pframes)
         *pframes = 0;
     if (n == 0)
@@ -352,14 +268,14 @@ static uint8_t run_device(if_fir_psd *c, const void *in, uint16_t *codes, float 
     HIP_TRY(c, hipSetDevice(c->device));
     if_fir::PsdArgs a{};
     a.in = in;
-    a.carry = c->d_carry[c->carry_cur];
-    a.carry_out = c->d_carry[c->carry_cur ^ 1];
+    a.carry = c->d_carry[c->st.carry_cur];
+    a.carry_out = c->d_carry[c->st.carry_cur ^ 1];
     a.window = c->d_window;
     a.twiddle = c->d_twiddle;
     a.bin_pos = c->d_bin_pos;
     a.work = c->d_work;
-    a.acc = c->d_acc[c->acc_cur];
-    a.acc_out = c->d_acc[c->acc_cur ^ 1];
+    a.acc = c->d_acc[c->st.acc_cur];
+    a.acc_out = c->d_acc[c->st.acc_cur ^ 1];
     a.codes = codes;
     a.power = power;
     a.N = c->N;
@@ -368,19 +284,19 @@ static uint8_t run_device(if_fir_psd *c, const void *in, uint16_t *codes, float 
     a.bins = c->bins;
     a.in_i16 = c->in_i16;
     a.n = (int64_t)n;
-    a.carried = (int64_t)c->carried;
+    a.carried = (int64_t)c->st.carried;
     a.plan = plan;
     a.scale = c->scale;
     a.ref_power = c->ref_power;
     a.device = c->device;
     a.stream = c->stream;
     HIP_TRY(c, if_fir::launch_psd(a));
-    c->position += n;
-    c->carried = plan.carry;
+    c->st.position += n;
+    c->st.carried = plan.carry;
     if (plan.carry > 0)
-        c->carry_cur ^= 1;
+        c->st.carry_cur ^= 1;
     if (plan.chunks > 0)
-        c->acc_cur ^= 1;
+        c->st.acc_cur ^= 1;
     if (pframes)
         *pframes = (uint32_t)plan.frames;
     return 1;
@@ -399,25 +315,21 @@ IF_FIR_API uint8_t if_fir_psd_process(if_fir_psd_t *pCtx, const void *pIQIn, uin
 {
     if (!pCtx)
         return 0;
-    if (ullSamples > pCtx->max_samples)
-    {
-        set_err(pCtx, "if_fir_psd_process: %llu samples exceed ullMaxSamples %llu of init", (unsigned long long)ullSamples,
-                (unsigned long long)pCtx->max_samples);
+    if (!if_fir::stream_ctx_fits(pCtx, "if_fir_psd_process", ullSamples))
         return 0;
-    }
     const uint64_t want = if_fir_psd_frame_count(pCtx, ullSamples);
     if ((ullSamples && !pIQIn) || (want && !pusBins))
     {
-        set_err(pCtx, "if_fir_psd_process: NULL buffer");
+        set_err(pCtx->err, "if_fir_psd_process: NULL buffer");
         return 0;
     }
     if (pulFrames)
         *pulFrames = 0;
     if (ullSamples == 0)
         return 1;
-    HIP_TRY(pCtx, hipSetDevice(pCtx->device));
     if (!pCtx->d_stage_in)
     {
+        HIP_TRY(pCtx, hipSetDevice(pCtx->device));
         const size_t values = (size_t)if_fir::psd_max_frames(pCtx->max_samples, (uint32_t)pCtx->H, (uint32_t)pCtx->K) * (size_t)pCtx->bins;
         hipError_t a = hipMalloc(&pCtx->d_stage_codes, values * sizeof(uint16_t));
         if (a == hipSuccess)
@@ -433,37 +345,25 @@ IF_FIR_API uint8_t if_fir_psd_process(if_fir_psd_t *pCtx, const void *pIQIn, uin
                 (void)hipFree(pCtx->d_stage_power);
             pCtx->d_stage_codes = nullptr;
             pCtx->d_stage_power = nullptr;
-            set_err(pCtx, "if_fir_psd_process: staging buffers: %s", hipGetErrorString(a));
+            set_err(pCtx->err, "if_fir_psd_process: staging buffers: %s", hipGetErrorString(a));
             return 0;
         }
     }
-    HIP_TRY(pCtx, hipMemcpyAsync(pCtx->d_stage_in, pIQIn, (size_t)ullSamples * (pCtx->in_i16 ? 4 : 8), hipMemcpyHostToDevice, pCtx->stream));
     uint32_t m = 0;
-    const uint64_t position = pCtx->position, carried = pCtx->carried;
-    const int carry_cur = pCtx->carry_cur, acc_cur = pCtx->acc_cur;
-    if (!run_device(pCtx, pCtx->d_stage_in, pCtx->d_stage_codes, pfPower ? pCtx->d_stage_power : nullptr, ullSamples, &m, "if_fir_psd_process"))
-    {
-        (void)hipStreamSynchronize(pCtx->stream);
+    if (!if_fir::stream_ctx_staged(
+            pCtx, "if_fir_psd_process", "frames", pCtx->d_stage_in, pIQIn, ullSamples, &pCtx->st,
+            [&] {
+                return run_device(pCtx, pCtx->d_stage_in, pCtx->d_stage_codes, pfPower ? pCtx->d_stage_power : nullptr, ullSamples, &m,
+                                  "if_fir_psd_process");
+            },
+            [&] {
+                const size_t values = (size_t)m * (size_t)pCtx->bins;
+                hipError_t e = m ? hipMemcpyAsync(pusBins, pCtx->d_stage_codes, values * sizeof(uint16_t), hipMemcpyDeviceToHost, pCtx->stream) : hipSuccess;
+                if (e == hipSuccess && m && pfPower)
+                    e = hipMemcpyAsync(pfPower, pCtx->d_stage_power, values * sizeof(float), hipMemcpyDeviceToHost, pCtx->stream);
+                return e;
+            }))
         return 0;
-    }
-    const size_t values = (size_t)m * (size_t)pCtx->bins;
-    hipError_t e = m ? hipMemcpyAsync(pusBins, pCtx->d_stage_codes, values * sizeof(uint16_t), hipMemcpyDeviceToHost, pCtx->stream) : hipSuccess;
-    if (e == hipSuccess && m && pfPower)
-        e = hipMemcpyAsync(pfPower, pCtx->d_stage_power, values * sizeof(float), hipMemcpyDeviceToHost, pCtx->stream);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(pCtx->stream);
-    if (e != hipSuccess)
-    {
-        // the frames did not reach the caller: the call failed, so the stream goes back to where it was (the carried samples and
-        // the accumulator of before the call are still in the buffers the kernels read)
-        pCtx->position = position;
-        pCtx->carried = carried;
-        pCtx->carry_cur = carry_cur;
-        pCtx->acc_cur = acc_cur;
-        set_err(pCtx, "if_fir_psd_process: copying the frames back failed: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        return 0;
-    }
     if (pulFrames)
         *pulFrames = m;
     return 1;
@@ -474,7 +374,7 @@ IF_FIR_API uint8_t if_fir_debug_psd_plan(const if_fir_psd_t *pCtx, uint64_t ullS
 {
     if_fir::PsdPlan plan;
     if (!pCtx || !pullPlan ||
-        !if_fir::psd_plan(pCtx->position, pCtx->carried, ullSamples, (uint32_t)pCtx->N, (uint32_t)pCtx->H, (uint32_t)pCtx->K, &plan))
+        !if_fir::psd_plan(pCtx->st.position, pCtx->st.carried, ullSamples, (uint32_t)pCtx->N, (uint32_t)pCtx->H, (uint32_t)pCtx->K, &plan))
         return 0;
     pullPlan[0] = plan.segments;
     pullPlan[1] = plan.chunks;

@@ -2,8 +2,6 @@
 // opaque context beside if_fir_ctx_t and if_fir_interp_t.  Same conventions: 1/0 status, a message per context, no CPU fallback.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -14,66 +12,37 @@
 #include "if_fir_debug.h"
 #endif
 #include "if_fir_resamp.h"
+#include "if_fir_stream_ctx.h"
 
 #define IF_FIR_API extern "C" __attribute__((visibility("default")))
 
-struct if_fir_resamp
+// the streaming state: what a call advances (and a failed if_fir_resamp_process puts back)
+struct resamp_state
 {
-    int device;
-    hipStream_t own_stream;
-    hipStream_t stream;
+    int hist_cur;
+    uint64_t consumed;        // input samples since init/reset
+};
+
+struct if_fir_resamp : if_fir::StreamCtx
+{
     int T, L, M;
     int ctaps;
-    int in_i16;
     float *d_taps;            // the phase-major table (resamp_build_taps)
     float2 *d_hist[2];        // the last hist_len input samples, float32, ping-pong
     int hist_len;
-    int hist_cur;
-    uint64_t consumed;        // input samples since init/reset
-    uint64_t max_samples;
+    resamp_state st;
     void *d_stage_in, *d_stage_out; // if_fir_resamp_process
     int grid_limit;           // development hook
-    mutable char err[256];
 };
 
+using if_fir::set_err;
 static thread_local char g_resamp_init_err[256] = "";
-
-static void set_err(const if_fir_resamp *ctx, const char *fmt, ...)
-{
-    char *dst = ctx ? ctx->err : g_resamp_init_err;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(dst, 256, fmt, ap);
-    va_end(ap);
-}
-
-#define HIP_TRY(ctx, call)                                                                                \
-    do                                                                                                    \
-    {                                                                                                     \
-        hipError_t e_ = (call);                                                                           \
-        if (e_ != hipSuccess)                                                                             \
-        {                                                                                                 \
-            set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);      \
-            return 0;                                                                                     \
-        }                                                                                                 \
-    } while (0)
 
 static void free_ctx(if_fir_resamp *c)
 {
     if (!c)
         return;
-    (void)hipSetDevice(c->device);
-    if (c->stream && c->stream != c->own_stream && hipStreamSynchronize(c->stream) != hipSuccess)
-        (void)hipGetLastError();
-    if (c->own_stream)
-    {
-        (void)hipStreamSynchronize(c->own_stream);
-        (void)hipStreamDestroy(c->own_stream);
-    }
-    void *bufs[] = {c->d_taps, c->d_hist[0], c->d_hist[1], c->d_stage_in, c->d_stage_out};
-    for (void *b : bufs)
-        if (b)
-            (void)hipFree(b);
+    if_fir::stream_ctx_close(c, {c->d_taps, c->d_hist[0], c->d_hist[1], c->d_stage_in, c->d_stage_out});
     delete c;
 }
 
@@ -88,80 +57,58 @@ static uint8_t resamp_init(if_fir_resamp_t **ppCtx, const float *pfTaps, uint32_
 {
     if (!ppCtx)
     {
-        set_err(nullptr, "if_fir_resamp_init: ppCtx is NULL");
+        set_err(g_resamp_init_err, "if_fir_resamp_init: ppCtx is NULL");
         return 0;
     }
     *ppCtx = nullptr;
     if (!pfTaps || ulTaps == 0 || ulTaps > IF_FIR_MAX_TAPS)
     {
-        set_err(nullptr, "if_fir_resamp_init: taps must be 1..%u (got %u)%s", IF_FIR_MAX_TAPS, ulTaps, pfTaps ? "" : ", pfTaps is NULL");
+        set_err(g_resamp_init_err, "if_fir_resamp_init: taps must be 1..%u (got %u)%s", IF_FIR_MAX_TAPS, ulTaps, pfTaps ? "" : ", pfTaps is NULL");
         return 0;
     }
     if (ulL < 1 || ulL > IF_FIR_MAX_INTERPOLATION)
     {
-        set_err(nullptr, "if_fir_resamp_init: interpolation must be 1..%u (got %u)", IF_FIR_MAX_INTERPOLATION, ulL);
+        set_err(g_resamp_init_err, "if_fir_resamp_init: interpolation must be 1..%u (got %u)", IF_FIR_MAX_INTERPOLATION, ulL);
         return 0;
     }
     if (ulM < 1 || ulM > IF_FIR_MAX_DECIMATION)
     {
-        set_err(nullptr, "if_fir_resamp_init: decimation must be 1..%u (got %u)", IF_FIR_MAX_DECIMATION, ulM);
+        set_err(g_resamp_init_err, "if_fir_resamp_init: decimation must be 1..%u (got %u)", IF_FIR_MAX_DECIMATION, ulM);
         return 0;
     }
     if (ullMax == 0 || ullMax > ((uint64_t)1 << 40) / ulL)
     {
-        set_err(nullptr, "if_fir_resamp_init: ullMaxSamples must be 1..2^40/L (got %llu)", (unsigned long long)ullMax);
+        set_err(g_resamp_init_err, "if_fir_resamp_init: ullMaxSamples must be 1..2^40/L (got %llu)", (unsigned long long)ullMax);
         return 0;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    {
-        (void)hipGetLastError();
-        set_err(nullptr, "if_fir_resamp_init: no HIP device");
+    if (!if_fir::stream_ctx_device_ok(g_resamp_init_err, "if_fir_resamp_init", lDevice))
         return 0;
-    }
-    if (lDevice < 0 || lDevice >= ndev)
-    {
-        set_err(nullptr, "if_fir_resamp_init: device %d does not exist (%d visible)", lDevice, ndev);
-        return 0;
-    }
     if_fir_resamp *c = new (std::nothrow) if_fir_resamp();
     if (!c)
     {
-        set_err(nullptr, "if_fir_resamp_init: out of host memory");
+        set_err(g_resamp_init_err, "if_fir_resamp_init: out of host memory");
         return 0;
     }
-    c->device = lDevice;
     c->T = (int)ulTaps;
     c->L = (int)ulL;
     c->M = (int)ulM;
     c->ctaps = ctaps;
-    c->max_samples = ullMax;
     c->hist_len = if_fir::resamp_hist_len(c->T, c->L);
     const if_fir::ResampShape shape = if_fir::resamp_shape(c->T, c->L, c->M);
     std::vector<float> table((size_t)shape.tap_entries * (ctaps ? 2 : 1));
     if_fir::resamp_build_taps(pfTaps, c->T, ctaps, c->L, table.data());
     const size_t hist_bytes = (size_t)(c->hist_len > 0 ? c->hist_len : 1) * sizeof(float2);
-    hipError_t e = hipSetDevice(lDevice);
-    if (e == hipSuccess)
-        e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
-    c->stream = c->own_stream;
-    if (e == hipSuccess)
-        e = hipMalloc(&c->d_taps, table.size() * sizeof(float));
-    if (e == hipSuccess)
-        e = hipMemcpy(c->d_taps, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice);
-    for (int i = 0; i < 2 && e == hipSuccess; i++)
-    {
-        e = hipMalloc(&c->d_hist[i], hist_bytes);
-        if (e == hipSuccess)
-            e = hipMemset(c->d_hist[i], 0, hist_bytes);
-    }
+    hipError_t e = if_fir::stream_ctx_open(c, lDevice, ullMax);
+    if_fir::stream_ctx_alloc_upload(e, &c->d_taps, table.data(), table.size() * sizeof(float));
+    for (int i = 0; i < 2; i++)
+        if_fir::stream_ctx_alloc_zeroed(e, &c->d_hist[i], hist_bytes);
     if (e == hipSuccess)
         e = hipMalloc(&c->d_stage_in, (size_t)ullMax * 8);
     if (e == hipSuccess)
         e = hipMalloc(&c->d_stage_out, (size_t)max_out(ullMax, ulL, ulM) * 8);
     if (e != hipSuccess)
     {
-        set_err(nullptr, "if_fir_resamp_init: %s", hipGetErrorString(e));
+        set_err(g_resamp_init_err, "if_fir_resamp_init: %s", hipGetErrorString(e));
         (void)hipGetLastError();
         free_ctx(c);
         return 0;
@@ -200,44 +147,29 @@ IF_FIR_API uint8_t if_fir_resamp_reset(if_fir_resamp_t *pCtx)
     for (int i = 0; i < 2 && pCtx->hist_len > 0; i++)
         HIP_TRY(pCtx, hipMemsetAsync(pCtx->d_hist[i], 0, (size_t)pCtx->hist_len * sizeof(float2), pCtx->stream));
     HIP_TRY(pCtx, hipStreamSynchronize(pCtx->stream));
-    pCtx->consumed = 0;
+    pCtx->st.consumed = 0;
     return 1;
 }
 
 IF_FIR_API uint8_t if_fir_resamp_set_input_format(if_fir_resamp_t *pCtx, uint32_t ulFormat)
 {
-    if (!pCtx)
-        return 0;
-    if (ulFormat > IF_FIR_INPUT_I16)
-    {
-        set_err(pCtx, "if_fir_resamp_set_input_format: unknown format %u", ulFormat);
-        return 0;
-    }
-    pCtx->in_i16 = (int)ulFormat; // (the history is kept as float32: a change of format keeps the stream)
-    return 1;
+    return if_fir::stream_ctx_set_input_format(pCtx, "if_fir_resamp_set_input_format", ulFormat);
 }
 
 IF_FIR_API uint8_t if_fir_resamp_set_stream(if_fir_resamp_t *pCtx, void *pStream)
 {
-    if (!pCtx)
-        return 0;
-    pCtx->stream = pStream ? static_cast<hipStream_t>(pStream) : pCtx->own_stream;
-    return 1;
+    return if_fir::stream_ctx_set_stream(pCtx, pStream);
 }
 
 IF_FIR_API uint8_t if_fir_resamp_synchronize(if_fir_resamp_t *pCtx)
 {
-    if (!pCtx)
-        return 0;
-    HIP_TRY(pCtx, hipSetDevice(pCtx->device));
-    HIP_TRY(pCtx, hipStreamSynchronize(pCtx->stream));
-    return 1;
+    return if_fir::stream_ctx_synchronize(pCtx);
 }
 
 IF_FIR_API uint64_t if_fir_resamp_out_count(const if_fir_resamp_t *pCtx, uint64_t ullSamples)
 {
     if_fir::ResampCall call;
-    if (!pCtx || !if_fir::resamp_call(pCtx->consumed, ullSamples, pCtx->L, pCtx->M, &call))
+    if (!pCtx || !if_fir::resamp_call(pCtx->st.consumed, ullSamples, pCtx->L, pCtx->M, &call))
         return 0;
     return call.count;
 }
@@ -245,30 +177,25 @@ IF_FIR_API uint64_t if_fir_resamp_out_count(const if_fir_resamp_t *pCtx, uint64_
 static uint8_t run_device(if_fir_resamp *c, const void *in, void *out, uint64_t n, uint64_t *pout, const char *who)
 {
     if_fir::ResampCall call;
-    if (n > ((uint64_t)1 << 40) / (uint64_t)c->L || !if_fir::resamp_call(c->consumed, n, c->L, c->M, &call))
+    if (n > ((uint64_t)1 << 40) / (uint64_t)c->L || !if_fir::resamp_call(c->st.consumed, n, c->L, c->M, &call))
     {
-        set_err(c, "%s: sample count too large", who);
+        set_err(c->err, "%s: sample count too large", who);
         return 0;
     }
     const uintptr_t in_mask = c->in_i16 ? 3 : 7, out_mask = 7;
     if (((uintptr_t)in & in_mask) || ((uintptr_t)out & out_mask))
     {
-        set_err(c, "%s: device pointers must be aligned to one sample: %u-byte (input) and %u-byte (output)", who,
+        set_err(c->err, "%s: device pointers must be aligned to one sample: %u-byte (input) and %u-byte (output)", who,
                 (unsigned)in_mask + 1, (unsigned)out_mask + 1);
         return 0;
     }
     if ((n && !in) || (call.count && !out))
     {
-        set_err(c, "%s: NULL device pointer", who);
+        set_err(c->err, "%s: NULL device pointer", who);
         return 0;
     }
-    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(c->stream, &capture) == hipSuccess && capture != hipStreamCaptureStatusNone)
-    {
-        set_err(c, "%s: the context's stream is being captured into a hipGraph; calls carry host-side streaming state and "
-                   "cannot be replayed", who);
+    if (if_fir::stream_ctx_capturing(c, who))
         return 0;
-    }
     if (n == 0)
     {
         if (pout)
@@ -279,8 +206,8 @@ static uint8_t run_device(if_fir_resamp *c, const void *in, void *out, uint64_t 
     if_fir::ResampArgs a{};
     a.in = in;
     a.out = out;
-    a.hist = c->d_hist[c->hist_cur];
-    a.hist_out = c->d_hist[c->hist_cur ^ 1];
+    a.hist = c->d_hist[c->st.hist_cur];
+    a.hist_out = c->d_hist[c->st.hist_cur ^ 1];
     a.taps = c->d_taps;
     a.T = c->T;
     a.L = c->L;
@@ -294,8 +221,8 @@ static uint8_t run_device(if_fir_resamp *c, const void *in, void *out, uint64_t 
     a.device = c->device;
     a.stream = c->stream;
     HIP_TRY(c, if_fir::launch_resamp(a));
-    c->consumed += n;
-    c->hist_cur ^= 1;
+    c->st.consumed += n;
+    c->st.hist_cur ^= 1;
     if (pout)
         *pout = call.count;
     return 1;
@@ -314,45 +241,24 @@ IF_FIR_API uint8_t if_fir_resamp_process(if_fir_resamp_t *pCtx, const void *pIQI
 {
     if (!pCtx)
         return 0;
-    if (ullSamples > pCtx->max_samples)
-    {
-        set_err(pCtx, "if_fir_resamp_process: %llu samples exceed ullMaxSamples %llu of init", (unsigned long long)ullSamples,
-                (unsigned long long)pCtx->max_samples);
+    if (!if_fir::stream_ctx_fits(pCtx, "if_fir_resamp_process", ullSamples))
         return 0;
-    }
     const uint64_t want = if_fir_resamp_out_count(pCtx, ullSamples);
     if ((ullSamples && !pIQIn) || (want && !pfIQOut))
     {
-        set_err(pCtx, "if_fir_resamp_process: NULL buffer");
+        set_err(pCtx->err, "if_fir_resamp_process: NULL buffer");
         return 0;
     }
     if (pullOutSamples)
         *pullOutSamples = 0;
     if (ullSamples == 0)
         return 1;
-    HIP_TRY(pCtx, hipSetDevice(pCtx->device));
-    HIP_TRY(pCtx, hipMemcpyAsync(pCtx->d_stage_in, pIQIn, (size_t)ullSamples * (pCtx->in_i16 ? 4 : 8), hipMemcpyHostToDevice, pCtx->stream));
     uint64_t m = 0;
-    const uint64_t consumed = pCtx->consumed;
-    const int hist_cur = pCtx->hist_cur;
-    if (!run_device(pCtx, pCtx->d_stage_in, pCtx->d_stage_out, ullSamples, &m, "if_fir_resamp_process"))
-    {
-        (void)hipStreamSynchronize(pCtx->stream);
+    if (!if_fir::stream_ctx_staged(
+            pCtx, "if_fir_resamp_process", "outputs", pCtx->d_stage_in, pIQIn, ullSamples, &pCtx->st,
+            [&] { return run_device(pCtx, pCtx->d_stage_in, pCtx->d_stage_out, ullSamples, &m, "if_fir_resamp_process"); },
+            [&] { return m ? hipMemcpyAsync(pfIQOut, pCtx->d_stage_out, (size_t)m * 8, hipMemcpyDeviceToHost, pCtx->stream) : hipSuccess; }))
         return 0;
-    }
-    hipError_t e = m ? hipMemcpyAsync(pfIQOut, pCtx->d_stage_out, (size_t)m * 8, hipMemcpyDeviceToHost, pCtx->stream) : hipSuccess;
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(pCtx->stream);
-    if (e != hipSuccess)
-    {
-        // the outputs did not reach the caller: the call failed, so the stream goes back to where it was (the history of before
-        // the call is still in the buffer the kernel read)
-        pCtx->consumed = consumed;
-        pCtx->hist_cur = hist_cur;
-        set_err(pCtx, "if_fir_resamp_process: copying the outputs back failed: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        return 0;
-    }
     if (pullOutSamples)
         *pullOutSamples = m;
     return 1;

@@ -163,69 +163,30 @@ def _load(path, dev):
     L.if_fir_mc_set_chunk_samples.restype = u8
     L.if_fir_mc_get_chunk_samples.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.if_fir_mc_get_chunk_samples.restype = u8
-    L.if_fir_interp_init.argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u64, i32]
-    L.if_fir_interp_init.restype = u8
-    L.if_fir_interp_init_complex.argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u64, i32]
-    L.if_fir_interp_init_complex.restype = u8
-    L.if_fir_interp_destroy.argtypes = [vp]
-    L.if_fir_interp_destroy.restype = None
-    for name in ("reset", "synchronize"):
-        getattr(L, "if_fir_interp_" + name).argtypes = [vp]
-        getattr(L, "if_fir_interp_" + name).restype = u8
-    for name in ("set_backend", "set_input_format"):
-        getattr(L, "if_fir_interp_" + name).argtypes = [vp, u32]
-        getattr(L, "if_fir_interp_" + name).restype = u8
+    # the streaming contexts (_StreamCtx): what the three families declare alike, then what each has of its own
+    for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_"):
+        for name, args, res in (("destroy", [vp], None), ("reset", [vp], u8), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
+                                ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p)):
+            getattr(L, prefix + name).argtypes = args
+            getattr(L, prefix + name).restype = res
+    for prefix, init_args in (("if_fir_interp_", [ctypes.POINTER(vp), f32p, u32, u32, u64, i32]),
+                              ("if_fir_resamp_", [ctypes.POINTER(vp), f32p, u32, u32, u32, u64, i32])):
+        for name, args, res in (("init", init_args, u8), ("init_complex", init_args, u8), ("out_count", [vp, u64], u64),
+                                ("process", [vp, vp, f32p, u64, ctypes.POINTER(u64)], u8),
+                                ("process_device", [vp, vp, vp, u64, ctypes.POINTER(u64)], u8)):
+            getattr(L, prefix + name).argtypes = args
+            getattr(L, prefix + name).restype = res
+    L.if_fir_interp_set_backend.argtypes = [vp, u32]
+    L.if_fir_interp_set_backend.restype = u8
     L.if_fir_interp_get_backend.argtypes = [vp]
     L.if_fir_interp_get_backend.restype = u32
     L.if_fir_interp_set_nco.argtypes = [vp, ctypes.c_double]
     L.if_fir_interp_set_nco.restype = u8
     L.if_fir_interp_get_nco.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     L.if_fir_interp_get_nco.restype = u8
-    L.if_fir_interp_set_stream.argtypes = [vp, vp]
-    L.if_fir_interp_set_stream.restype = u8
-    L.if_fir_interp_last_error.argtypes = [vp]
-    L.if_fir_interp_last_error.restype = ctypes.c_char_p
-    L.if_fir_interp_out_count.argtypes = [vp, u64]
-    L.if_fir_interp_out_count.restype = u64
-    L.if_fir_interp_process.argtypes = [vp, vp, f32p, u64, ctypes.POINTER(u64)]
-    L.if_fir_interp_process.restype = u8
-    L.if_fir_interp_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
-    L.if_fir_interp_process_device.restype = u8
-    L.if_fir_resamp_init.argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u32, u64, i32]
-    L.if_fir_resamp_init.restype = u8
-    L.if_fir_resamp_init_complex.argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u32, u64, i32]
-    L.if_fir_resamp_init_complex.restype = u8
-    L.if_fir_resamp_destroy.argtypes = [vp]
-    L.if_fir_resamp_destroy.restype = None
-    for name in ("reset", "synchronize"):
-        getattr(L, "if_fir_resamp_" + name).argtypes = [vp]
-        getattr(L, "if_fir_resamp_" + name).restype = u8
-    L.if_fir_resamp_set_input_format.argtypes = [vp, u32]
-    L.if_fir_resamp_set_input_format.restype = u8
-    L.if_fir_resamp_set_stream.argtypes = [vp, vp]
-    L.if_fir_resamp_set_stream.restype = u8
-    L.if_fir_resamp_last_error.argtypes = [vp]
-    L.if_fir_resamp_last_error.restype = ctypes.c_char_p
-    L.if_fir_resamp_out_count.argtypes = [vp, u64]
-    L.if_fir_resamp_out_count.restype = u64
-    L.if_fir_resamp_process.argtypes = [vp, vp, f32p, u64, ctypes.POINTER(u64)]
-    L.if_fir_resamp_process.restype = u8
-    L.if_fir_resamp_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
-    L.if_fir_resamp_process_device.restype = u8
     u16p = ctypes.POINTER(ctypes.c_uint16)
     L.if_fir_psd_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(PsdConfig), f32p, u64, i32]
     L.if_fir_psd_init.restype = u8
-    L.if_fir_psd_destroy.argtypes = [vp]
-    L.if_fir_psd_destroy.restype = None
-    for name in ("reset", "synchronize"):
-        getattr(L, "if_fir_psd_" + name).argtypes = [vp]
-        getattr(L, "if_fir_psd_" + name).restype = u8
-    L.if_fir_psd_set_input_format.argtypes = [vp, u32]
-    L.if_fir_psd_set_input_format.restype = u8
-    L.if_fir_psd_set_stream.argtypes = [vp, vp]
-    L.if_fir_psd_set_stream.restype = u8
-    L.if_fir_psd_last_error.argtypes = [vp]
-    L.if_fir_psd_last_error.restype = ctypes.c_char_p
     L.if_fir_psd_frame_count.argtypes = [vp, u64]
     L.if_fir_psd_frame_count.restype = u64
     L.if_fir_psd_process.argtypes = [vp, vp, u64, u16p, f32p, ctypes.POINTER(u32)]
@@ -491,9 +452,65 @@ class IfFir:
         return host
 
 
-class IfFirInterp:
+class _StreamCtx:
+    """What IfFirInterp, IfFirResamp and IfFirPsd share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
+    calls the three families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
+    __init__, self._L, self._ctx and self._i16."""
+    _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
+
+    def _c(self, name):
+        return getattr(self._L, self._PREFIX + name)
+
+    def _check(self, ok):
+        if not ok:
+            raise IfFirError(self._c("last_error")(self._ctx).decode())
+
+    def close(self):
+        if self._ctx:
+            self._c("destroy")(self._ctx)
+            self._ctx = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        self._check(self._c("reset")(self._ctx))
+
+    def set_input_format(self, fmt):
+        self._check(self._c("set_input_format")(self._ctx, int(fmt)))
+        self._i16 = (int(fmt) == INPUT_I16)
+
+    def set_stream(self, stream_handle):
+        self._check(self._c("set_stream")(self._ctx, ctypes.c_void_p(stream_handle or None)))
+
+    def synchronize(self):
+        self._check(self._c("synchronize")(self._ctx))
+
+    def _host_input(self, iq):
+        """(contiguous interleaved float32 -- or int16 after set_input_format(INPUT_I16) -- array, sample count) of a host array"""
+        iq = np.asarray(iq)
+        if self._i16:
+            iq = np.ascontiguousarray(iq, dtype=np.int16).reshape(-1)
+        else:
+            if np.iscomplexobj(iq):
+                iq = np.ascontiguousarray(iq.astype(np.complex64)).view(np.float32)
+            iq = np.ascontiguousarray(iq, dtype=np.float32).reshape(-1)
+        return iq, iq.size // 2
+
+
+class IfFirInterp(_StreamCtx):
     """One if_fir_interp_t: upsample by `interpolation`, filter, optionally mix up (docs/SPEC.md §6).  Methods mirror the C
     entry points; N input samples give N * interpolation outputs."""
+    _PREFIX = "if_fir_interp_"
 
     def __init__(self, taps, interpolation, max_samples=1 << 20, device=0, backend=None, complex_taps=False, dev=False):
         self._L = dev_lib() if dev else lib()
@@ -510,43 +527,15 @@ class IfFirInterp:
         if not init(ctypes.byref(self._ctx), _f32p(taps), taps.size // 2 if complex_taps else taps.size, self.interpolation,
                     int(max_samples), int(device)):
             self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._L.if_fir_interp_last_error(None).decode())
+            raise IfFirError(self._c("last_error")(None).decode())
         if backend is not None:
             self.set_backend(backend)
-
-    def _check(self, ok):
-        if not ok:
-            raise IfFirError(self._L.if_fir_interp_last_error(self._ctx).decode())
-
-    def close(self):
-        if self._ctx:
-            self._L.if_fir_interp_destroy(self._ctx)
-            self._ctx = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def reset(self):
-        self._check(self._L.if_fir_interp_reset(self._ctx))
 
     def set_backend(self, backend):
         self._check(self._L.if_fir_interp_set_backend(self._ctx, int(backend)))
 
     def get_backend(self):
         return int(self._L.if_fir_interp_get_backend(self._ctx))
-
-    def set_input_format(self, fmt):
-        self._check(self._L.if_fir_interp_set_input_format(self._ctx, int(fmt)))
-        self._i16 = (int(fmt) == INPUT_I16)
 
     def set_nco(self, freq):
         """if_fir_interp_set_nco(): mix the OUTPUT up by exp(+j 2 pi f n), n = absolute output index; 0 = off."""
@@ -557,26 +546,13 @@ class IfFirInterp:
         self._check(self._L.if_fir_interp_get_nco(self._ctx, ctypes.byref(f)))
         return float(f.value)
 
-    def set_stream(self, stream_handle):
-        self._check(self._L.if_fir_interp_set_stream(self._ctx, ctypes.c_void_p(stream_handle or None)))
-
-    def synchronize(self):
-        self._check(self._L.if_fir_interp_synchronize(self._ctx))
-
     def out_count(self, samples):
         return int(self._L.if_fir_interp_out_count(self._ctx, int(samples)))
 
     def process(self, iq):
         """if_fir_interp_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in,
         interleaved float32 out."""
-        iq = np.asarray(iq)
-        if self._i16:
-            iq = np.ascontiguousarray(iq, dtype=np.int16).reshape(-1)
-        else:
-            if np.iscomplexobj(iq):
-                iq = np.ascontiguousarray(iq.astype(np.complex64)).view(np.float32)
-            iq = np.ascontiguousarray(iq, dtype=np.float32).reshape(-1)
-        n = iq.size // 2
+        iq, n = self._host_input(iq)
         out = np.empty(2 * self.out_count(n), dtype=np.float32)
         m = ctypes.c_uint64(0)
         dummy = np.zeros(2, dtype=np.float32)
@@ -621,9 +597,10 @@ def debug_interp_plan(taps, interpolation):
     return int(rows.value), int(hist.value), bool(ok.value)
 
 
-class IfFirResamp:
+class IfFirResamp(_StreamCtx):
     """One if_fir_resamp_t: change the rate by interpolation / decimation in one polyphase pass (docs/SPEC.md §7).  Methods
     mirror the C entry points; how many outputs a call emits depends on the stream position (out_count)."""
+    _PREFIX = "if_fir_resamp_"
 
     def __init__(self, taps, interpolation, decimation, max_samples=1 << 20, device=0, complex_taps=False, dev=False):
         self._L = dev_lib() if dev else lib()
@@ -641,41 +618,7 @@ class IfFirResamp:
         if not init(ctypes.byref(self._ctx), _f32p(taps), taps.size // 2 if complex_taps else taps.size, self.interpolation,
                     self.decimation, int(max_samples), int(device)):
             self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._L.if_fir_resamp_last_error(None).decode())
-
-    def _check(self, ok):
-        if not ok:
-            raise IfFirError(self._L.if_fir_resamp_last_error(self._ctx).decode())
-
-    def close(self):
-        if self._ctx:
-            self._L.if_fir_resamp_destroy(self._ctx)
-            self._ctx = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def reset(self):
-        self._check(self._L.if_fir_resamp_reset(self._ctx))
-
-    def set_input_format(self, fmt):
-        self._check(self._L.if_fir_resamp_set_input_format(self._ctx, int(fmt)))
-        self._i16 = (int(fmt) == INPUT_I16)
-
-    def set_stream(self, stream_handle):
-        self._check(self._L.if_fir_resamp_set_stream(self._ctx, ctypes.c_void_p(stream_handle or None)))
-
-    def synchronize(self):
-        self._check(self._L.if_fir_resamp_synchronize(self._ctx))
+            raise IfFirError(self._c("last_error")(None).decode())
 
     def out_count(self, samples):
         """if_fir_resamp_out_count(): outputs of a call with `samples` inputs at the current stream position."""
@@ -684,14 +627,7 @@ class IfFirResamp:
     def process(self, iq):
         """if_fir_resamp_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in,
         interleaved float32 out."""
-        iq = np.asarray(iq)
-        if self._i16:
-            iq = np.ascontiguousarray(iq, dtype=np.int16).reshape(-1)
-        else:
-            if np.iscomplexobj(iq):
-                iq = np.ascontiguousarray(iq.astype(np.complex64)).view(np.float32)
-            iq = np.ascontiguousarray(iq, dtype=np.float32).reshape(-1)
-        n = iq.size // 2
+        iq, n = self._host_input(iq)
         out = np.empty(2 * self.out_count(n), dtype=np.float32)
         m = ctypes.c_uint64(0)
         dummy = np.zeros(2, dtype=np.float32)
@@ -722,10 +658,11 @@ class IfFirResamp:
         return self.debug_config(self._grid_limit)
 
 
-class IfFirPsd:
+class IfFirPsd(_StreamCtx):
     """One if_fir_psd_t: averaged periodogram of an IQ stream as frames of uint16 spectrum codes, the layout wb_detect reads
     (docs/SPEC.md §8).  Methods mirror the C entry points; how many frames a call emits depends on the stream position
     (frame_count)."""
+    _PREFIX = "if_fir_psd_"
 
     def __init__(self, size, hop, segments, first_bin, bins, ref_power=1.0, window=None, input_format=INPUT_F32,
                  max_samples=1 << 20, device=0, dev=False):
@@ -743,41 +680,7 @@ class IfFirPsd:
             wp = _f32p(window)
         if not self._L.if_fir_psd_init(ctypes.byref(self._ctx), ctypes.byref(cfg), wp, int(max_samples), int(device)):
             self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._L.if_fir_psd_last_error(None).decode())
-
-    def _check(self, ok):
-        if not ok:
-            raise IfFirError(self._L.if_fir_psd_last_error(self._ctx).decode())
-
-    def close(self):
-        if self._ctx:
-            self._L.if_fir_psd_destroy(self._ctx)
-            self._ctx = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def reset(self):
-        self._check(self._L.if_fir_psd_reset(self._ctx))
-
-    def set_input_format(self, fmt):
-        self._check(self._L.if_fir_psd_set_input_format(self._ctx, int(fmt)))
-        self._i16 = (int(fmt) == INPUT_I16)
-
-    def set_stream(self, stream_handle):
-        self._check(self._L.if_fir_psd_set_stream(self._ctx, ctypes.c_void_p(stream_handle or None)))
-
-    def synchronize(self):
-        self._check(self._L.if_fir_psd_synchronize(self._ctx))
+            raise IfFirError(self._c("last_error")(None).decode())
 
     def frame_count(self, samples):
         """if_fir_psd_frame_count(): frames of a call with `samples` samples at the current stream position."""
@@ -786,14 +689,7 @@ class IfFirPsd:
     def process(self, iq, want_power=True):
         """if_fir_psd_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in;
         returns ((frames, bins) uint16 codes, (frames, bins) float32 power or None)."""
-        iq = np.asarray(iq)
-        if self._i16:
-            iq = np.ascontiguousarray(iq, dtype=np.int16).reshape(-1)
-        else:
-            if np.iscomplexobj(iq):
-                iq = np.ascontiguousarray(iq.astype(np.complex64)).view(np.float32)
-            iq = np.ascontiguousarray(iq, dtype=np.float32).reshape(-1)
-        n = iq.size // 2
+        iq, n = self._host_input(iq)
         frames = self.frame_count(n)
         codes = np.empty((frames, self.bins), dtype=np.uint16)
         power = np.empty((frames, self.bins), dtype=np.float32) if want_power else None

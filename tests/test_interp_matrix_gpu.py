@@ -182,17 +182,24 @@ def test_single_calls_round_a_block(gpu_ok, fir, oracle, rows, form, L):
             check(oracle, y, ref, ("single", rows, form, L, n))
 
 
+SHORT_PIECES = [(T, L, i16, backend) for T, L in ((3073, 1), (3073, 4), (2049, 2)) for i16 in (False, True)
+                for backend in ("overlap-save", "generic")]
+# one tap at an L that does not divide 64: the generic kernel reads ceil((T - 1) / L) = 0 samples of the history
+SHORT_PIECES.append((1, 3, False, "generic"))
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("backend", ["overlap-save", "generic"])
-@pytest.mark.parametrize("i16", [False, True])
-@pytest.mark.parametrize("T,L", [(3073, 1), (3073, 4), (2049, 2)])
+@pytest.mark.parametrize("T,L,i16,backend", SHORT_PIECES)
 def test_pieces_shorter_than_the_history(gpu_ok, fir, oracle, T, L, i16, backend):
-    """hist_len = overlap / L input samples (3072, 768, 1024): a piece shorter than that shifts the old history instead of
-    replacing it.  Overlap-save in its production form (small for L = 4, full for L = 1, 2)."""
-    hist = overlap_of(T) // L
+    """hist_len = ceil(overlap / L) input samples (3072, 768, 1024): a piece shorter than that shifts the old history instead of
+    replacing it.  Overlap-save in its production form (small for L = 4, full for L = 1, 2).  T = 1 is the filter with no
+    history: 1000 samples in one call, and as 1 + 999, are taps[0] times the zero-stuffed input, exactly."""
+    hist = -(-overlap_of(T) // L)
     assert fir.debug_interp_plan(T, L)[1] == hist
     sizes = [1, 1, 5, 100, hist - 1, 1, hist + 1, 2, hist // 2, 3, 2 * hist + 7, hist - 100, hist]
     n = sum(sizes) + 1501
+    if T == 1:
+        sizes, n = [1], 1000
     raw, x = signal(oracle, n, i16)
     taps = edge_taps(T, L, False)
     form = "generic" if backend == "generic" else ("small" if L >= 4 else "full")
@@ -202,6 +209,8 @@ def test_pieces_shorter_than_the_history(gpu_ok, fir, oracle, T, L, i16, backend
             f.reset()
             one = f.process(raw)
             assert np.array_equal(y, one), np.max(np.abs(y - one))
+    if T == 1:
+        assert np.array_equal(y, taps[0] * zero_stuffed(x, L))
     check(oracle, y, reference(oracle, taps, x, L), ("short pieces", T, L, i16, backend))
 
 
