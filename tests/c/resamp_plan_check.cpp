@@ -7,7 +7,8 @@
 // p_r + L dq_r = t0 + r M, every tap index touched is < T or lands on a zero pad, and every input index touched by the call's
 // first and last L outputs lies in [-(K-1), N).
 //
-// `resamp_plan_check table L T` prints the table of taps h[k] = k + 1 (rows of KP entries) for the Python test to compare.
+// `resamp_plan_check table L T` prints the table of taps h[k] = k + 1 (rows of KP entries) for the Python test to compare;
+// `resamp_plan_check shape L M T` prints K, W, B, tile_out and tile_in of resamp_shape.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -39,6 +40,15 @@ int main(int argc, char **argv)
         for (int p = 0; p < L; p++, printf("\n"))
             for (int j = 0; j < KP; j++)
                 printf("%g ", g[(size_t)p * KP + j]);
+        return 0;
+    }
+    if (argc == 5 && argv[1][0] == 's')
+    {
+        const int L = atoi(argv[2]), M = atoi(argv[3]), T = atoi(argv[4]);
+        if (L < 1 || L > RESAMP_MAX_L || M < 1 || M > RESAMP_MAX_M || T < 1 || T > RESAMP_MAX_TAPS)
+            return 2;
+        const ResampShape s = resamp_shape(T, L, M);
+        printf("%d %d %d %d %d\n", s.K, s.W, s.B, s.tile_out, s.tile_in);
         return 0;
     }
     unsigned long long shapes = 0, calls = 0;

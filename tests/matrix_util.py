@@ -1,5 +1,5 @@
 """Taps, streams and the comparison shared by the per-instantiation matrices (tests/test_interp_matrix_gpu.py,
-tests/test_fft_matrix_gpu.py).  Plain functions, like tests/bank_ref.py.
+tests/test_fft_matrix_gpu.py, tests/test_resamp_gpu.py).  Plain functions, like tests/bank_ref.py.
 
 The taps are not a windowed design (whose end taps are zero, and the next ones 1e-6 of the peak): the first and the last tap
 are the largest of the set, so one tap wrapped into the kept region or one sample missing from the history costs about
@@ -29,6 +29,28 @@ def edge_taps(T, L, complex_taps, seed=0):
     h[0] = 1.0
     if T > 1:
         h[-1] = -1j if complex_taps else -1.0
+    h *= np.sqrt(L / np.sum(np.abs(h) ** 2))
+    if complex_taps:
+        return as_iq(h).astype(np.float32)
+    return h.real.astype(np.float32)
+
+
+def row_edge_taps(T, L, complex_taps, seed=0):
+    """edge_taps for a polyphase filter with rows g[p][j] = h[p + j L]: seeded normal taps, |h| <= 0.5 inside, every phase's
+    first tap (the first min(L, T) taps) of magnitude 1 with alternating sign, every phase's highest tap (the last min(L, T)
+    taps) the same negated (complex: times -j), the whole set scaled to sum |h|^2 = L.  With T <= L every phase has one tap,
+    which is both ends and keeps the first form; L = 1 gives edge_taps' ends, first tap +, last tap - (complex: -j).
+    float32; complex taps interleaved (re, im)."""
+    rng = np.random.default_rng([T, L, int(complex_taps), seed, 77])
+    h = rng.standard_normal(T).astype(np.complex128)
+    if complex_taps:
+        h = h + 1j * rng.standard_normal(T)
+    h *= 0.5 / np.max(np.abs(h))
+    e = min(L, T)
+    sgn = np.where(np.arange(e) % 2 == 0, 1.0, -1.0).astype(np.complex128)
+    h[:e] = sgn
+    if T > e:
+        h[T - e:] = (-1j if complex_taps else -1.0) * sgn[::-1]
     h *= np.sqrt(L / np.sum(np.abs(h) ** 2))
     if complex_taps:
         return as_iq(h).astype(np.float32)

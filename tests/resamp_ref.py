@@ -16,6 +16,23 @@ def out_count(c, n, L, M):
     return ceil_div((c + n) * L, M) - ceil_div(c * L, M)
 
 
+def tile_shape(T, L, M):
+    """(K, tile_out, tile_in) of the kernel's tile, restated from resamp_shape (csrc/if_fir_resamp_plan.h): K phase taps; the
+    largest multiple of L within 256 lanes, 4 outputs per lane, capped to the periods whose inputs and K - 1 samples of overlap
+    fit 8192 LDS samples.  tests/test_resamp_host.py holds it to the header, tests/test_resamp_gpu.py to the library."""
+    K = ceil_div(T, L)
+    B = min((256 // L) * 4, (8192 - (K - 1)) // M)
+    return K, B * L, B * M
+
+
+def stream_len(T, L, M):
+    """the shortest stream of the loud-row-end tests: three whole tiles and a ragged part, and never shorter than two phase
+    rows: a stream shorter than K - 1 samples (64/1 with 4096 taps: 49 samples against K = 64) would put only the zeros of
+    the start under every phase's highest tap"""
+    K, tile_out, _ = tile_shape(T, L, M)
+    return max(((3 * tile_out + 17) * M) // L + 1, 2 * K + 17)
+
+
 def as_c(iq):
     iq = np.asarray(iq, dtype=np.float64).reshape(-1, 2)
     return iq[:, 0] + 1j * iq[:, 1]

@@ -6,7 +6,9 @@ import functools
 import numpy as np
 import pytest
 
+import matrix_util
 import resamp_ref
+from matrix_util import row_edge_taps
 
 TOL = 1e-6
 GUARD = 64          # float32 words behind the last output
@@ -15,6 +17,21 @@ SENTINEL = 12345.0
 # filter, T < L (phases without a tap), a call that emits fewer outputs than one period, a single tap
 MATRIX = ((3, 2, 95), (2, 3, 63), (5, 7, 255), (4, 6, 33), (1, 4, 255), (4, 1, 255), (1, 1, 31), (64, 63, 1537), (63, 64, 1537),
           (64, 1, 4096), (4, 3, 4096), (1, 3, 1023), (7, 5, 3), (3, 64, 100), (5, 2, 1))
+
+# the rows of test_matrix_with_loud_row_ends (taps of matrix_util.row_edge_taps, streams of resamp_ref.stream_len): MATRIX, then
+LOUD_MATRIX = MATRIX + (
+    # K = 4096, the longest history: the LDS fit caps the tile to 64 periods = 64 outputs, so 64 lanes of one of the four
+    # places work, and the tile's window is 8191 of 8192 samples
+    (1, 64, 4096),
+    # capped tiles whose output count is no multiple of the lane count W: the mask of a lane's places cuts inside a place
+    (2, 64, 4096), (8, 64, 1000),
+    # a common factor of 4 with a capped tile; gcd = L, one phase reached
+    (4, 64, 4096), (64, 64, 4096),
+    # the highest segment and the remainder after the unroll by 8: K = 2, 7, 8, 9, 15, 16, 17, 33 phase taps give a highest
+    # segment of 2, 7, 8, 9, 15, 16, 1, 1 taps and remainders of 2, 7, 0, 1, 7, 0, 1, 1
+    (3, 2, 6), (3, 2, 21), (3, 2, 24), (3, 2, 27), (3, 2, 45), (3, 2, 48), (3, 2, 51), (3, 2, 99),
+    # the last row entries of two of the three phases are padding zeros
+    (3, 2, 22), (3, 2, 49))
 
 
 @pytest.fixture(scope="module")
@@ -62,23 +79,44 @@ def reference(fir, L, M, T, ct, i16, n):
     return ref
 
 
+def loud_signal(n, i16):
+    """matrix_util.signal: (what the context is fed, the same samples as float32); int16 with full-scale samples"""
+    import __graft_entry__ as g
+    return matrix_util.signal(g.load_oracle(), n, i16)
+
+
+@functools.lru_cache(maxsize=None)
+def loud_reference(L, M, T, ct, i16, n):
+    ref = resamp_ref.resample_f64(row_edge_taps(T, L, ct), loud_signal(n, i16)[1], L, M, ct)
+    ref.setflags(write=False)
+    return ref
+
+
 def cases():
     """every ratio with {real, complex} taps x {float32, int16}: each row meets all four kernel instantiations"""
     return [(L, M, T, ct, i16) for (L, M, T) in MATRIX for ct in (False, True) for i16 in (False, True)]
 
 
-def run_device(torch, f, raw, pieces, i16):
-    """feed `raw` from ONE device buffer in consecutive pieces (sample-aligned offsets); returns (outputs, counts)"""
-    n = raw.size // 2
-    din = torch.from_numpy(np.ascontiguousarray(raw)).cuda()
+def run_device(torch, f, raw, pieces, i16, formats=None):
+    """feed `raw` from ONE device buffer in consecutive pieces (sample-aligned offsets); returns (outputs, counts).  With
+    `formats` (one input format per piece, set before that piece) `raw` maps each format to the stream in that format: the
+    same values in every one, one device buffer each."""
+    both = {None: raw} if formats is None else raw
+    n = next(iter(both.values())).size // 2
+    assert all(v.size == 2 * n for v in both.values())
+    din = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in both.items()}
     total = resamp_ref.out_count(0, n, f.interpolation, f.decimation)
     buf = torch.full((2 * total + GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
-    in_bytes = 4 if i16 else 8
     pos = done = 0
     counts = []
-    for s in pieces:
+    for k, s in enumerate(pieces):
+        if formats is not None:
+            f.set_input_format(formats[k])
+        src = din[None if formats is None else formats[k]]
+        in_bytes = 2 * src.element_size()
+        assert formats is not None or in_bytes == (4 if i16 else 8)
         want = f.out_count(s)
-        got = f.process_device(din.data_ptr() + in_bytes * pos, buf.data_ptr() + 8 * done, s)
+        got = f.process_device(src.data_ptr() + in_bytes * pos, buf.data_ptr() + 8 * done, s)
         assert got == want == resamp_ref.out_count(pos, s, f.interpolation, f.decimation), (pos, s, got, want)
         counts.append(got)
         pos += s
@@ -110,6 +148,79 @@ def test_matrix_against_float64(gpu_ok, fir, oracle, torch_cuda, L, M, T, ct, i1
     assert np.array_equal(yd, y)
 
 
+def loud_cases():
+    return [(L, M, T, ct, i16) for (L, M, T) in LOUD_MATRIX for ct in (False, True) for i16 in (False, True)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("L,M,T,ct,i16", loud_cases())
+def test_matrix_with_loud_row_ends(gpu_ok, fir, oracle, torch_cuda, L, M, T, ct, i16):
+    """every phase's first and highest tap are the largest of the filter (tests/test_resamp_host.py: dropping one of them costs
+    more than 1e-2), on the shortest stream with three whole tiles and a ragged one; the int16 stream carries full-scale
+    samples.  Host and device path, one cut that is a multiple of neither M (where M > 1) nor the tile's input count."""
+    K, tile_out, tile_in = resamp_ref.tile_shape(T, L, M)
+    n = resamp_ref.stream_len(T, L, M)
+    raw, _ = loud_signal(n, i16)
+    ref = loud_reference(L, M, T, ct, i16, n)
+    cut = n // 3
+    while cut % tile_in == 0 or (M > 1 and cut % M == 0):
+        cut += 1
+    assert 0 < cut < n
+    with fir.IfFirResamp(row_edge_taps(T, L, ct), L, M, max_samples=n, complex_taps=ct, dev=True) as f:
+        assert f.tile_outputs() == tile_out
+        assert resamp_ref.out_count(0, n, L, M) > 3 * tile_out and resamp_ref.out_count(0, n, L, M) % tile_out
+        if i16:
+            f.set_input_format(fir.INPUT_I16)
+        y = np.concatenate([f.process(raw[:2 * cut]), f.process(raw[2 * cut:])])
+        f.reset()
+        yd, _ = run_device(torch_cuda, f, raw, [cut, n - cut], i16)
+    assert y.size == ref.size == 2 * resamp_ref.out_count(0, n, L, M)
+    l2, mx = oracle.err_metrics(y, ref)
+    print("loud-rows L=%d M=%d T=%d complex=%d i16=%d: l2=%.3g max=%.3g" % (L, M, T, ct, i16, l2, mx))
+    assert l2 <= TOL and mx <= TOL, (l2, mx)
+    assert np.array_equal(yd, y)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ct,i16", [(False, False), (True, True)])
+@pytest.mark.parametrize("L,M,T", [(3, 2, 95), (1, 3, 1023), (1, 64, 4096), (63, 64, 1537)])
+def test_pieces_around_the_history_with_loud_row_ends(gpu_ok, fir, oracle, torch_cuda, L, M, T, ct, i16):
+    """calls one shorter than, as long as and one longer than the K - 1 samples of history, then of 1, 0, forty times 1, M - 1
+    and L samples, then the rest: in the short ones the first workgroup builds the next history from the old history and
+    the call.  Bit for bit the one-call run, which meets float64.  Then the same stream as float32 and, from a cut inside
+    a tile on, as int16: a change of format keeps the stream (csrc/if_fir_stream_ctx.h)."""
+    K, tile_out, tile_in = resamp_ref.tile_shape(T, L, M)
+    head = [K - 2, K - 1, K, 1, 0] + 40 * [1] + [M - 1, L]
+    n = max(resamp_ref.stream_len(T, L, M), sum(head) + tile_in + K + 17)
+    raw, _ = loud_signal(n, i16)
+    xi, xf = loud_signal(n, True)
+    both = {fir.INPUT_F32: xf, fir.INPUT_I16: xi}
+    with fir.IfFirResamp(row_edge_taps(T, L, ct), L, M, max_samples=n, complex_taps=ct, dev=True) as f:
+        assert f.tile_outputs() == tile_out
+        if i16:
+            f.set_input_format(fir.INPUT_I16)
+        one, _ = run_device(torch_cuda, f, raw, [n], i16)
+        l2, mx = oracle.err_metrics(one, loud_reference(L, M, T, ct, i16, n))
+        print("loud-pieces L=%d M=%d T=%d complex=%d i16=%d: l2=%.3g max=%.3g" % (L, M, T, ct, i16, l2, mx))
+        assert l2 <= TOL and mx <= TOL, (l2, mx)
+        f.reset()
+        y, counts = run_device(torch_cuda, f, raw, head + [n - sum(head)], i16)
+        assert counts[4] == 0 and np.array_equal(y, one)
+        # float32 first; int16 from inside the first tile on, in a call shorter than the history, then the rest
+        if not i16:
+            f.reset()
+            one, _ = run_device(torch_cuda, f, xf, [n], False)
+        pieces = [tile_in // 2 + 1, 0, K - 2, n - tile_in // 2 - K + 1]
+        assert pieces[0] % tile_in and min(pieces) >= 0
+        f.reset()
+        y, _ = run_device(torch_cuda, f, both, pieces, None, formats=[fir.INPUT_F32, fir.INPUT_F32, fir.INPUT_I16, fir.INPUT_I16])
+        assert np.array_equal(y, one)
+        f.reset()
+        f.set_input_format(fir.INPUT_I16)
+        y, _ = run_device(torch_cuda, f, xi, [n], True)
+        assert np.array_equal(y, one)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("L,M", [(3, 2), (2, 3), (5, 7), (63, 64)])
 def test_split_invariance_bit_for_bit(gpu_ok, fir, torch_cuda, L, M):
@@ -135,20 +246,35 @@ def test_split_invariance_bit_for_bit(gpu_ok, fir, torch_cuda, L, M):
         assert np.array_equal(y, one)
 
 
+# (L, M, T, loud, complex taps, int16): the designed filters in real taps and float32; with row_edge_taps the tiles that the LDS
+# fit caps (127 periods of 3/64, the 64 outputs of 1/64 with 4096 taps, 126 periods of 8/64: a grid-stride loop over such tiles
+# is where tile * tile_in has to stay 64-bit), and the instantiation furthest from the first one on a full and on a capped tile
+TILE_EDGES = [pytest.param(3, 2, 95, False, False, False, id="3-2-95"), pytest.param(5, 7, 255, False, False, False, id="5-7-255"),
+              pytest.param(1, 3, 1023, False, False, False, id="1-3-1023"),
+              pytest.param(3, 64, 100, True, False, False, id="3-64-100-loud"),
+              pytest.param(1, 64, 4096, True, False, False, id="1-64-4096-loud"),
+              pytest.param(8, 64, 1000, True, False, False, id="8-64-1000-loud"),
+              pytest.param(3, 2, 95, True, True, True, id="3-2-95-loud-complex-i16"),
+              pytest.param(3, 64, 100, True, True, True, id="3-64-100-loud-complex-i16")]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("L,M,T", [(3, 2, 95), (5, 7, 255), (1, 3, 1023)])
-def test_tile_and_grid_edges(gpu_ok, fir, torch_cuda, L, M, T):
+@pytest.mark.parametrize("L,M,T,loud,ct,i16", TILE_EDGES)
+def test_tile_and_grid_edges(gpu_ok, fir, torch_cuda, L, M, T, loud, ct, i16):
     """output counts one less than, equal to and one more than 1 tile and 5 tiles (from a reset, L > M reaches only the counts
     ceil(n L / M): the next one up then stands in); the grid capped to 1 and to 3 workgroups gives the bits of the uncapped run"""
-    taps = taps_for(fir, T, L, M, False)
-    with fir.IfFirResamp(taps, L, M, max_samples=1 << 16, dev=True) as f:
+    taps = row_edge_taps(T, L, ct) if loud else taps_for(fir, T, L, M, ct)
+    with fir.IfFirResamp(taps, L, M, max_samples=1 << 16, complex_taps=ct, dev=True) as f:
+        if i16:
+            f.set_input_format(fir.INPUT_I16)
         tile = f.tile_outputs()
+        assert tile == resamp_ref.tile_shape(T, L, M)[1]
         assert tile > 0 and tile % L == 0
         n_for = lambda outs: (outs - 1) * M // L + 1          # the fewest inputs that emit `outs` outputs
         n_max = n_for(5 * tile + 1)
         seen = set()
-        x, _ = signal(n_max, False)
-        ref_all = resamp_ref.resample_f64(taps, x, L, M)
+        raw, x = loud_signal(n_max, i16) if loud else signal(n_max, i16)
+        ref_all = resamp_ref.resample_f64(taps, x, L, M, ct)
         for want in (tile - 1, tile, tile + 1, 5 * tile - 1, 5 * tile, 5 * tile + 1):
             n = n_for(want)
             outs = resamp_ref.out_count(0, n, L, M)
@@ -158,7 +284,7 @@ def test_tile_and_grid_edges(gpu_ok, fir, torch_cuda, L, M, T):
             for limit in (0, 1, 3):
                 f.debug_config(grid_limit=limit)
                 f.reset()
-                y, _ = run_device(torch_cuda, f, x[:2 * n], [n], False)
+                y, _ = run_device(torch_cuda, f, raw[:2 * n], [n], i16)
                 runs.append(y)
             assert np.array_equal(runs[0], runs[1]) and np.array_equal(runs[0], runs[2]), outs
             ref = ref_all[:2 * outs]
@@ -243,3 +369,39 @@ def test_against_interpolate_then_decimate(gpu_ok, fir, oracle, L, M, T):
     for name, got in (("resampler", y), ("chain", chain)):
         l2, mx = oracle.err_metrics(got, ref)
         assert l2 <= TOL and mx <= TOL, (name, l2, mx)
+
+
+@pytest.mark.gpu
+def test_random_configurations_against_float64(gpu_ok, fir, oracle, torch_cuda):
+    """40 seeded draws: L and M uniform in 1..64, T log-uniform in 1..4096, complex taps and int16 input drawn per case, taps
+    loud at both ends of every phase row, the stream of resamp_ref.stream_len (at most 2^17 samples), 2 to 6 pieces with one
+    of 0 samples.  Every draw meets float64 within SPEC §3, and its pieces give the bits of the single call."""
+    rng = np.random.default_rng(20261019)
+    worst = {"l2": (0.0, None), "max": (0.0, None)}
+    for draw in range(40):
+        L, M = (int(v) for v in rng.integers(1, 65, 2))
+        T = min(4096, max(1, int(round(np.exp(rng.uniform(0.0, np.log(4096.0)))))))
+        ct, i16 = bool(rng.integers(2)), bool(rng.integers(2))
+        n = min(resamp_ref.stream_len(T, L, M), 1 << 17)
+        cuts = np.sort(rng.choice(np.arange(1, n), int(rng.integers(2, 7)) - 2, replace=False))
+        pieces = [int(v) for v in np.diff(np.concatenate([[0], cuts, [n]]))]
+        pieces.insert(int(rng.integers(len(pieces) + 1)), 0)
+        case = "draw %d: L=%d M=%d T=%d complex=%d i16=%d n=%d pieces=%s" % (draw, L, M, T, ct, i16, n, pieces)
+        assert 2 <= len(pieces) <= 6 and sum(pieces) == n, case
+        raw, x = loud_signal(n, i16)
+        taps = row_edge_taps(T, L, ct, seed=draw)
+        ref = resamp_ref.resample_f64(taps, x, L, M, ct)
+        with fir.IfFirResamp(taps, L, M, max_samples=n, complex_taps=ct) as f:
+            if i16:
+                f.set_input_format(fir.INPUT_I16)
+            one, _ = run_device(torch_cuda, f, raw, [n], i16)
+            f.reset()
+            y, _ = run_device(torch_cuda, f, raw, pieces, i16)
+        l2, mx = oracle.err_metrics(one, ref)
+        for name, v in (("l2", l2), ("max", mx)):
+            if v > worst[name][0]:
+                worst[name] = (v, case)
+        assert l2 <= TOL and mx <= TOL, (case, l2, mx)
+        assert np.array_equal(y, one), case
+    for name in ("l2", "max"):
+        print("resamp-random worst %s=%.3g at %s" % (name, worst[name][0], worst[name][1]))
