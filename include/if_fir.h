@@ -266,6 +266,55 @@ uint8_t if_fir_interp_process(if_fir_interp_t *pCtx, const void *pIQIn, float *p
 uint8_t if_fir_interp_process_device(if_fir_interp_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples,
                                      uint64_t *pullOutSamples);
 
+/* ---- channel combiner (docs/SPEC.md §9; BUILD-DEFINED) --------------------------------------------------------------------
+ * The transmit counterpart of the channelizer: C baseband streams (1..64), each interpolated by L (1..64) with ONE prototype
+ * filter and mixed UP to its own centre, summed into one stream in one pass:
+ *     u_c[n] = x_c[n/L] if n mod L == 0, else 0;   y[n] = sum_c exp(+j*2*pi*P_c*n/2^32) sum_k h[k] u_c[n-k]
+ * n = absolute OUTPUT index since init/reset (mod 2^32 in the rotation), P_c = centre c quantised to a 32-bit phase word as the
+ * interpolator's NCO: what C interpolator contexts with their NCOs at the centres compute, added.  A call brings N samples for
+ * EVERY channel and emits exactly N*L outputs; process(a||b) == process(a); process(b) within the SPEC tolerance wherever the
+ * stream is cut.  Taps are used as given (image rejection needs a gain of L); real or complex, T <= 4096; float32 or int16 input,
+ * the same for all channels; float32 I/Q output.  Two channels may share a centre; a centre of 0 means no rotation.
+ * Backends: IF_FIR_BACKEND_HIP_FFT (AUTO's pick for L in {4, 8, 16, 32, 64} and T <= 3073: overlap-save, one inverse transform
+ * and one store for all channels) and IF_FIR_BACKEND_HIP_GENERIC (any L, T and C: one output per thread); others are refused.
+ * Errors: 0 + if_fir_combiner_last_error(); a failed call leaves the context usable and its stream position unchanged.  Calls on
+ * a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_combiner if_fir_combiner_t;
+#define IF_FIR_COMBINER_MAX_CHANNELS 64u
+
+/* pdCentre: ulChannels centres in cycles per OUTPUT sample, |f| <= 0.5 */
+uint8_t if_fir_combiner_init(if_fir_combiner_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulInterpolation,
+                             uint32_t ulChannels, const double *pdCentre, uint64_t ullMaxSamples, int32_t lDevice);
+/* complex taps: ulTaps interleaved (re, im) pairs */
+uint8_t if_fir_combiner_init_complex(if_fir_combiner_t **ppCtx, const float *pfTapsIQ, uint32_t ulTaps, uint32_t ulInterpolation,
+                                     uint32_t ulChannels, const double *pdCentre, uint64_t ullMaxSamples, int32_t lDevice);
+void if_fir_combiner_destroy(if_fir_combiner_t *pCtx);
+/* zero every channel's history and the output index */
+uint8_t if_fir_combiner_reset(if_fir_combiner_t *pCtx);
+uint8_t if_fir_combiner_set_backend(if_fir_combiner_t *pCtx, uint32_t ulBackend);
+uint32_t if_fir_combiner_get_backend(const if_fir_combiner_t *pCtx); /* the resolved (non-AUTO) backend */
+/* IF_FIR_INPUT_F32 or IF_FIR_INPUT_I16 (value = int16 * 2^-15); the histories are float32, so a change keeps the stream */
+uint8_t if_fir_combiner_set_input_format(if_fir_combiner_t *pCtx, uint32_t ulFormat);
+/* all centres at once; takes effect from the next call as if set since the last reset (phase-continuous in n).  Waits for the
+ * context's stream (the multiply tables are rebuilt and uploaded). */
+uint8_t if_fir_combiner_set_centres(if_fir_combiner_t *pCtx, const double *pdCentre);
+/* the quantised centres, ulChannels values */
+uint8_t if_fir_combiner_get_centres(const if_fir_combiner_t *pCtx, double *pdCentre);
+uint8_t if_fir_combiner_set_stream(if_fir_combiner_t *pCtx, void *pStream);
+uint8_t if_fir_combiner_synchronize(if_fir_combiner_t *pCtx);
+const char *if_fir_combiner_last_error(const if_fir_combiner_t *pCtx);
+/* = ullSamples * L */
+uint64_t if_fir_combiner_out_count(const if_fir_combiner_t *pCtx, uint64_t ullSamples);
+/* host pointers, synchronous: ppIQIn[c] = ullSamples samples of channel c; ullSamples <= ullMaxSamples of init; pfIQOut holds
+ * ullSamples * L samples */
+uint8_t if_fir_combiner_process(if_fir_combiner_t *pCtx, const void *const *ppIQIn, float *pfIQOut, uint64_t ullSamples,
+                                uint64_t *pullOutSamples);
+/* ppDevIn: a HOST array of ulChannels device pointers (handed to the kernel by value: the call makes no allocation, copy or
+ * synchronise of its own); asynchronous on the context's stream.  Alignment as the interpolator's: overlap-save backend one
+ * sample (input 8 bytes, 4 for int16; output 8 bytes), generic backend 16 bytes.  pDevOut holds ullSamples * L samples. */
+uint8_t if_fir_combiner_process_device(if_fir_combiner_t *pCtx, const void *const *ppDevIn, void *pDevOut, uint64_t ullSamples,
+                                       uint64_t *pullOutSamples);
+
 /* ---- rational resampler (docs/SPEC.md §7; BUILD-DEFINED) -----------------------------------------------------------------
  * Changes a stream's rate by L/M (L, M in 1..64, used as given: a common factor is legal) in ONE polyphase pass:
  *     u[n] = x[n/L] if n mod L == 0, else 0;   v[n] = sum_k h[k] u[n-k];   y[m] = v[m*M]

@@ -91,6 +91,17 @@ uint32_t if_fir_debug_interp_tables(const float *pfTaps, uint32_t ulTaps, uint32
  * the overlap-save backend serves the pair; 0 = taps or interpolation outside if_fir_interp_init's range */
 uint8_t if_fir_debug_interp_plan(uint32_t ulTaps, uint32_t ulInterpolation, uint32_t *pulRows, uint32_t *pulHistLen,
                                  uint32_t *pbFftOk);
+/* channel combiner (if_fir_combiner_t): ulGridLimit = at most this many workgroups (0 = the launcher's choice; same results: one
+ * workgroup then walks several blocks at test size) */
+uint8_t if_fir_debug_combiner_config(if_fir_combiner_t *pCtx, uint32_t ulGridLimit);
+/* channel combiner: set the count of input samples per channel consumed since reset (the output index of the next call is
+ * ullSamples * L; the histories are kept), as the interpolator's seek */
+uint8_t if_fir_debug_combiner_seek(if_fir_combiner_t *pCtx, uint64_t ullSamples);
+/* host-only: the split of a centre's phase word P = G 2^20 + r (*pulGrid = G in 0..4095, *plResidual = r in -2^19..2^19-1) and the
+ * combiner's multiply table for it, FFT_4096(h[k] exp(j 2 pi r k / 2^32)) / 4096, as 4096 (re, im) pairs (ulOutFloats >= 8192);
+ * returns the floats written, 0 when the taps are not served by the overlap-save kernel or |dCentre| > 0.5 */
+uint32_t if_fir_debug_combiner_tables(const float *pfTaps, uint32_t ulTaps, uint32_t bComplexTaps, double dCentre, uint32_t *pulGrid,
+                                      int32_t *plResidual, float *pfOut, uint32_t ulOutFloats);
 /* resampler (if_fir_resamp_t): ulGridLimit = at most this many workgroups (0 = the launcher's choice; same results: one
  * workgroup then walks many tiles at test size); *pulTileOutputs (may be NULL) receives the outputs of one tile of this context */
 uint8_t if_fir_debug_resamp_config(if_fir_resamp_t *pCtx, uint32_t ulGridLimit, uint32_t *pulTileOutputs);

@@ -38,13 +38,18 @@ EXPORTS = [
     "if_fir_resamp_process", "if_fir_resamp_process_device",
     "if_fir_psd_init", "if_fir_psd_destroy", "if_fir_psd_reset", "if_fir_psd_set_input_format", "if_fir_psd_set_stream",
     "if_fir_psd_synchronize", "if_fir_psd_last_error", "if_fir_psd_frame_count", "if_fir_psd_process", "if_fir_psd_process_device",
+    "if_fir_combiner_init", "if_fir_combiner_init_complex", "if_fir_combiner_destroy", "if_fir_combiner_reset", "if_fir_combiner_set_backend",
+    "if_fir_combiner_get_backend", "if_fir_combiner_set_input_format", "if_fir_combiner_set_centres", "if_fir_combiner_get_centres",
+    "if_fir_combiner_set_stream", "if_fir_combiner_synchronize", "if_fir_combiner_last_error", "if_fir_combiner_out_count",
+    "if_fir_combiner_process", "if_fir_combiner_process_device",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
                "if_fir_debug_bank_plan", "if_fir_debug_bank_tail", "if_fir_debug_fft_schedule",
                "if_fir_mc_debug_plan", "if_fir_debug_queue_faults",
                "if_fir_debug_interp_config", "if_fir_debug_interp_seek", "if_fir_debug_interp_tables", "if_fir_debug_interp_plan",
-               "if_fir_debug_resamp_config", "if_fir_debug_psd_plan"]
+               "if_fir_debug_resamp_config", "if_fir_debug_psd_plan",
+               "if_fir_debug_combiner_config", "if_fir_debug_combiner_seek", "if_fir_debug_combiner_tables"]
 MC_ID_BYTES = 128
 
 
@@ -163,8 +168,8 @@ def _load(path, dev):
     L.if_fir_mc_set_chunk_samples.restype = u8
     L.if_fir_mc_get_chunk_samples.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.if_fir_mc_get_chunk_samples.restype = u8
-    # the streaming contexts (_StreamCtx): what the three families declare alike, then what each has of its own
-    for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_"):
+    # the streaming contexts (_StreamCtx): what the families declare alike, then what each has of its own
+    for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_"):
         for name, args, res in (("destroy", [vp], None), ("reset", [vp], u8), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
                                 ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p)):
             getattr(L, prefix + name).argtypes = args
@@ -184,6 +189,24 @@ def _load(path, dev):
     L.if_fir_interp_set_nco.restype = u8
     L.if_fir_interp_get_nco.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     L.if_fir_interp_get_nco.restype = u8
+    f64p = ctypes.POINTER(ctypes.c_double)
+    for name in ("init", "init_complex"):
+        getattr(L, "if_fir_combiner_" + name).argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u32, f64p, u64, i32]
+        getattr(L, "if_fir_combiner_" + name).restype = u8
+    L.if_fir_combiner_set_backend.argtypes = [vp, u32]
+    L.if_fir_combiner_set_backend.restype = u8
+    L.if_fir_combiner_get_backend.argtypes = [vp]
+    L.if_fir_combiner_get_backend.restype = u32
+    L.if_fir_combiner_set_centres.argtypes = [vp, f64p]
+    L.if_fir_combiner_set_centres.restype = u8
+    L.if_fir_combiner_get_centres.argtypes = [vp, f64p]
+    L.if_fir_combiner_get_centres.restype = u8
+    L.if_fir_combiner_out_count.argtypes = [vp, u64]
+    L.if_fir_combiner_out_count.restype = u64
+    L.if_fir_combiner_process.argtypes = [vp, ctypes.POINTER(vp), f32p, u64, ctypes.POINTER(u64)]
+    L.if_fir_combiner_process.restype = u8
+    L.if_fir_combiner_process_device.argtypes = [vp, ctypes.POINTER(vp), vp, u64, ctypes.POINTER(u64)]
+    L.if_fir_combiner_process_device.restype = u8
     u16p = ctypes.POINTER(ctypes.c_uint16)
     L.if_fir_psd_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(PsdConfig), f32p, u64, i32]
     L.if_fir_psd_init.restype = u8
@@ -194,6 +217,12 @@ def _load(path, dev):
     L.if_fir_psd_process_device.argtypes = [vp, vp, u64, vp, vp, ctypes.POINTER(u32)]
     L.if_fir_psd_process_device.restype = u8
     if dev:
+        L.if_fir_debug_combiner_config.argtypes = [vp, u32]
+        L.if_fir_debug_combiner_config.restype = u8
+        L.if_fir_debug_combiner_seek.argtypes = [vp, u64]
+        L.if_fir_debug_combiner_seek.restype = u8
+        L.if_fir_debug_combiner_tables.argtypes = [f32p, u32, u32, ctypes.c_double, ctypes.POINTER(u32), ctypes.POINTER(i32), f32p, u32]
+        L.if_fir_debug_combiner_tables.restype = u32
         L.if_fir_debug_psd_plan.argtypes = [vp, u64, ctypes.POINTER(u64)]
         L.if_fir_debug_psd_plan.restype = u8
         L.if_fir_debug_resamp_config.argtypes = [vp, u32, ctypes.POINTER(u32)]
@@ -453,7 +482,7 @@ class IfFir:
 
 
 class _StreamCtx:
-    """What IfFirInterp, IfFirResamp and IfFirPsd share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
+    """What IfFirInterp, IfFirResamp, IfFirPsd and IfFirCombiner share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
     calls the three families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
     __init__, self._L, self._ctx and self._i16."""
     _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
@@ -595,6 +624,103 @@ def debug_interp_plan(taps, interpolation):
         raise IfFirError("if_fir_debug_interp_plan: %d taps, interpolation %d are outside if_fir_interp_init's range"
                          % (int(taps), int(interpolation)))
     return int(rows.value), int(hist.value), bool(ok.value)
+
+
+class IfFirCombiner(_StreamCtx):
+    """One if_fir_combiner_t: C baseband streams, each interpolated by `interpolation` with one prototype filter and mixed up to
+    its own centre, summed into one stream in one pass (docs/SPEC.md §9).  Methods mirror the C entry points; N input samples per
+    channel give N * interpolation outputs."""
+    _PREFIX = "if_fir_combiner_"
+
+    def __init__(self, taps, interpolation, centres, max_samples=1 << 20, device=0, backend=None, complex_taps=False, dev=False):
+        self._L = dev_lib() if dev else lib()
+        taps = np.asarray(taps)
+        if np.iscomplexobj(taps):
+            taps = np.ascontiguousarray(taps.astype(np.complex64)).view(np.float32)
+            complex_taps = True
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1)
+        self._ctx = ctypes.c_void_p()
+        self.taps = taps
+        self.interpolation = int(interpolation)
+        self.channels = int(centres.size)
+        self._i16 = False
+        init = self._L.if_fir_combiner_init_complex if complex_taps else self._L.if_fir_combiner_init
+        if not init(ctypes.byref(self._ctx), _f32p(taps), taps.size // 2 if complex_taps else taps.size, self.interpolation,
+                    self.channels, centres.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(max_samples), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._c("last_error")(None).decode())
+        if backend is not None:
+            self.set_backend(backend)
+
+    def set_backend(self, backend):
+        self._check(self._L.if_fir_combiner_set_backend(self._ctx, int(backend)))
+
+    def get_backend(self):
+        return int(self._L.if_fir_combiner_get_backend(self._ctx))
+
+    def set_centres(self, centres):
+        """if_fir_combiner_set_centres(): all centres at once, from the next call, as if set since the last reset."""
+        centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1)
+        if centres.size != self.channels:
+            raise IfFirError("if_fir_combiner_set_centres takes %d centres (got %d)" % (self.channels, centres.size))
+        self._check(self._L.if_fir_combiner_set_centres(self._ctx, centres.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+
+    def get_centres(self):
+        f = np.zeros(self.channels, dtype=np.float64)
+        self._check(self._L.if_fir_combiner_get_centres(self._ctx, f.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return f
+
+    def out_count(self, samples):
+        return int(self._L.if_fir_combiner_out_count(self._ctx, int(samples)))
+
+    def process(self, iqs):
+        """if_fir_combiner_process(): one host array per channel (interleaved float32 / complex64, or int16 pairs after
+        set_input_format(INPUT_I16)), all of one length, in; interleaved float32 out."""
+        if len(iqs) != self.channels:
+            raise IfFirError("if_fir_combiner_process takes %d channels (got %d)" % (self.channels, len(iqs)))
+        arrs = [self._host_input(iq) for iq in iqs]
+        n = arrs[0][1]
+        if any(a[1] != n for a in arrs):
+            raise IfFirError("if_fir_combiner_process: every channel brings the same number of samples")
+        out = np.empty(2 * self.out_count(n), dtype=np.float32)
+        m = ctypes.c_uint64(0)
+        dummy = np.zeros(2, dtype=np.float32)
+        ptrs = (ctypes.c_void_p * self.channels)(*[a[0].ctypes.data if n else dummy.ctypes.data for a in arrs])
+        self._check(self._L.if_fir_combiner_process(self._ctx, ptrs, _f32p(out if out.size else dummy), n, ctypes.byref(m)))
+        assert m.value * 2 == out.size
+        return out
+
+    def process_device(self, dev_ins, dev_out, samples):
+        """if_fir_combiner_process_device(): raw device pointers (ints), one per channel, asynchronous.  Returns the output
+        sample count."""
+        if len(dev_ins) != self.channels:
+            raise IfFirError("if_fir_combiner_process_device takes %d channels (got %d)" % (self.channels, len(dev_ins)))
+        m = ctypes.c_uint64(0)
+        ptrs = (ctypes.c_void_p * self.channels)(*[int(p) for p in dev_ins])
+        self._check(self._L.if_fir_combiner_process_device(self._ctx, ptrs, ctypes.c_void_p(dev_out), int(samples), ctypes.byref(m)))
+        return int(m.value)
+
+    def debug_config(self, grid_limit=0):
+        """if_fir_debug_combiner_config() (development library: construct with dev=True)."""
+        self._check(self._L.if_fir_debug_combiner_config(self._ctx, int(grid_limit)))
+
+    def debug_seek(self, samples):
+        """if_fir_debug_combiner_seek() (development library): the next call's first output index becomes samples * L."""
+        self._check(self._L.if_fir_debug_combiner_seek(self._ctx, int(samples)))
+
+
+def debug_combiner_tables(taps, centre, complex_taps=False):
+    """if_fir_debug_combiner_tables(): (G, r, the combiner's multiply table for the residual r as complex64) of a centre
+    (host-only, no GPU)."""
+    taps = np.ascontiguousarray(taps, dtype=np.float32)
+    t = taps.size // 2 if complex_taps else taps.size
+    out = np.zeros(2 * 4096, dtype=np.float32)
+    grid, res = ctypes.c_uint32(0), ctypes.c_int32(0)
+    if dev_lib().if_fir_debug_combiner_tables(_f32p(taps), t, 1 if complex_taps else 0, float(centre), ctypes.byref(grid),
+                                              ctypes.byref(res), _f32p(out), out.size) != out.size:
+        raise IfFirError("if_fir_debug_combiner_tables: %d taps at centre %r are not served by the overlap-save kernel" % (t, centre))
+    return int(grid.value), int(res.value), out.view(np.complex64)
 
 
 class IfFirResamp(_StreamCtx):

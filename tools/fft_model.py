@@ -636,6 +636,57 @@ def interp_block(xin, h, L, small=True):
     return stockham(Z, inverse=True)
 
 
+# ---- the channel combiner's block (csrc/if_fir_combiner.hip, fir_combiner_kernel) ----
+# P = G 2^20 + r: per channel the block's 4096/L inputs times exp(j 2 pi G n0 / 4096) exp(j theta_r n), the small forward
+# transform, times H_r read modulo 4096/L and moved by G bins, summed in the registers of the thread that owns the bin; the first
+# inverse pass starts from those registers.
+
+
+def combiner_block(xins, h, L, words, n0):
+    """One overlap-save block of the combiner: xins[c] = channel c's 4096/L input samples, words[c] = its phase word, n0 = the
+    absolute output index of the block's first point.  Thread t owns the bins t + 256 q + 1024 r (q, r = 0..3), the inputs
+    j + r 1024, j = t + 256 q, of its first inverse butterflies; returns the 4096 circular outputs."""
+    nf = N // L
+    h = np.asarray(h, dtype=np.complex128)
+    tw = np.exp(-2j * np.pi * np.arange(N) / N)
+    acc = np.zeros((256, 4, 4), dtype=np.complex128)   # [thread][q][r]
+    t = np.arange(256)
+    for xin, P in zip(xins, words):
+        G = ((P + (1 << 19)) % (1 << 32)) >> 20
+        r_res = (P - (G << 20)) % (1 << 32)
+        r_res -= (1 << 32) if r_res >= (1 << 31) else 0
+        Hr = np.fft.fft(h * np.exp(2j * np.pi * r_res * np.arange(h.size) / 2.0 ** 32), N) / N
+        s = np.conj(tw[(G * (n0 % N)) % N])
+        n = (n0 + np.arange(nf) * L) % (1 << 32)
+        w = s * np.exp(2j * np.pi * ((n * (r_res % (1 << 32))) % (1 << 32)) / 2.0 ** 32)
+        X = stockham(np.asarray(xin, dtype=np.complex128) * w)
+        for q in range(4):
+            for r in range(4):
+                k = (t + q * 256 + r * (N // 4) - G) & (N - 1)
+                acc[:, q, r] += Hr[k] * X[k & (nf - 1)]
+    buf = np.zeros(N, dtype=np.complex128)
+    for q in range(4):          # the first inverse pass (ns = 1, no twiddles): input j + r 1024 -> position 4 j + r
+        j = t + q * 256
+        v = acc[:, q, :]
+        V = np.stack([sum(v[:, a] * np.conj(tw[(a * r * (N // 4)) % N]) for a in range(4)) for r in range(4)], axis=1)
+        for r in range(4):
+            buf[4 * j + r] = V[:, r]
+    x, ns = buf, 4
+    twi = tw.conj()
+    while ns < N:               # the remaining radix-4 inverse passes, as stockham()
+        nr = N // 4
+        y = np.empty_like(x)
+        for j in range(nr):
+            k = j & (ns - 1)
+            v = np.array([x[j + r * nr] * twi[(r * k * (N // (ns * 4))) % N] for r in range(4)])
+            V = np.array([sum(v[a] * twi[(a * r * (N // 4)) % N] for a in range(4)) for r in range(4)])
+            for r in range(4):
+                y[(j - k) * 4 + k + r * ns] = V[r]
+        x = y
+        ns *= 4
+    return x
+
+
 def main_interp():
     rng = np.random.default_rng(11)
     h = rng.standard_normal(255)
