@@ -19,7 +19,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
 #include <cmath>
 #include <vector>
 
@@ -39,8 +38,7 @@ __device__ __forceinline__ void cb_write_history(const CombinerChans &ch, int C,
     if (blockIdx.x != 0 || !hist_out)
         return;
     for (int c = 0; c < C; c++)
-        for (int i = threadIdx.x; i < hist_len; i += blockDim.x)
-            hist_out[c * hist_len + i] = ip_load<I16>(ch.in[c], hist + c * hist_len, hist_len, N, N - hist_len + i);
+        ip_history<I16>(ch.in[c], hist + c * hist_len, hist_out + c * hist_len, hist_len, N);
 }
 
 #if !defined(IF_FIR_COMBINER_ROWS) // ================= host side + the generic kernel =================
@@ -87,52 +85,17 @@ __global__ __launch_bounds__(INTERP_THREADS) void fir_combiner_generic_kernel(co
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride)
     {
-        // per channel as fir_interp_generic_kernel: output i of the call has phase i mod L, tap k meets input (i - k) / L; partial
-        // sums of 32 taps added with a compensated (two-sum) addition.  The channels are added the same way, in ascending order.
+        // per channel as fir_interp_generic_kernel; the channels are added the same way (two-sum), in ascending order
         const uint32_t n32 = first_out + (uint32_t)i;
         float yr = 0.f, yi = 0.f, er = 0.f, ei = 0.f;
         for (int c = 0; c < C; c++)
         {
-            const void *in = ch.in[c];
-            const float2 *hc = hist + c * hist_len;
-            float ar = 0.f, ai = 0.f, cr = 0.f, ci = 0.f;
-            int k = (int)(i % L);
-            while (k < T)
-            {
-                float pr = 0.f, pi = 0.f;
-                for (int s = 0; s < 32 && k < T; s++, k += L)
-                {
-                    const float2 x = ip_load<I16>(in, hc, hist_len, N, (i - k) / L);
-                    if constexpr (CT)
-                    {
-                        const float hr = taps[2 * k], hi = taps[2 * k + 1];
-                        pr = fmaf(hr, x.x, fmaf(-hi, x.y, pr));
-                        pi = fmaf(hr, x.y, fmaf(hi, x.x, pi));
-                    }
-                    else
-                    {
-                        const float h = taps[k];
-                        pr = fmaf(h, x.x, pr);
-                        pi = fmaf(h, x.y, pi);
-                    }
-                }
-                const float sr = ar + pr, si = ai + pi;
-                const float br = sr - ar, bi = si - ai;
-                cr += (ar - (sr - br)) + (pr - br);
-                ci += (ai - (si - bi)) + (pi - bi);
-                ar = sr;
-                ai = si;
-            }
-            float2 y = make_float2(ar + cr, ai + ci);
+            float2 y = ip_phase_sum<I16, CT>(ch.in[c], hist + c * hist_len, hist_len, taps, T, L, N, i);
             const uint32_t word = ((uint32_t)ch.G[c] << 20) + ch.rword[c];
             if (word)
                 y = ip_cmul(y, nco_phasor(word * n32));
-            const float sr = yr + y.x, si = yi + y.y;
-            const float br = sr - yr, bi = si - yi;
-            er += (yr - (sr - br)) + (y.x - br);
-            ei += (yi - (si - bi)) + (y.y - bi);
-            yr = sr;
-            yi = si;
+            two_sum_add(yr, er, y.x);
+            two_sum_add(yi, ei, y.y);
         }
         out[i] = make_float2(yr + er, yi + ei);
     }
@@ -141,14 +104,8 @@ __global__ __launch_bounds__(INTERP_THREADS) void fir_combiner_generic_kernel(co
 template <bool I16, bool CT>
 static hipError_t launch_generic_t(const CombinerArgs &a)
 {
-    int64_t groups = (a.M + INTERP_THREADS - 1) / INTERP_THREADS;
-    if (groups < 1)
-        groups = 1; // (the history is written even by a call without outputs)
-    if (groups > 65536)
-        groups = 65536;
-    if (a.grid_limit > 0 && groups > a.grid_limit)
-        groups = a.grid_limit;
-    hipLaunchKernelGGL((fir_combiner_generic_kernel<I16, CT>), dim3((unsigned)groups), dim3(INTERP_THREADS), 0, a.stream, a.ch, a.C,
+    const unsigned groups = stream_generic_groups(a.M, INTERP_THREADS, a.grid_limit);
+    hipLaunchKernelGGL((fir_combiner_generic_kernel<I16, CT>), dim3(groups), dim3(INTERP_THREADS), 0, a.stream, a.ch, a.C,
                        static_cast<float2 *>(a.out), a.hist, a.hist_out, a.hist_len, a.taps, a.T, a.L, a.N, a.M, a.first_out);
     return hipGetLastError();
 }
@@ -166,7 +123,7 @@ hipError_t launch_combiner_generic(const CombinerArgs &a)
 
 // (single ds_read_b64 LDS reads, like the interpolator's units)
 template <int OVL_ROWS, bool I16>
-__global__ __launch_bounds__(INTERP_THREADS, 2) IF_FIR_INTERP_SINGLE_READS void fir_combiner_kernel(
+__global__ __launch_bounds__(INTERP_THREADS, 2) IF_FIR_SINGLE_READS void fir_combiner_kernel(
     const CombinerChans ch, int C, float2 *__restrict__ out, const float2 *__restrict__ hist, float2 *__restrict__ hist_out, int hist_len,
     const float2 *__restrict__ H, const float2 *__restrict__ tw, int L, int64_t N, int64_t M, int64_t nblocks, uint32_t first_out)
 {
@@ -209,15 +166,7 @@ __global__ __launch_bounds__(INTERP_THREADS, 2) IF_FIR_INTERP_SINGLE_READS void 
                 buf[p] = ip_cmul(x, w);
             }
             __syncthreads();
-            int ns = 1;
-            if (nf & 0x2aaa) // log2(nf) odd: one radix-2 pass first
-            {
-                ip_pass<2, false>(nf, ns, tw, lds, to_lds);
-                ns = 2;
-            }
-#pragma unroll 1
-            for (; ns < nf; ns *= 4)
-                ip_pass<4, false>(nf, ns, tw, lds, to_lds);
+            ip_forward(nf, tw, lds, to_lds);
             // ---- Z_c = H_r X_c (X_c read modulo nf) moved by G bins, added to the sums; 1/4096 is in H_r ----
 #pragma unroll
             for (int q = 0; q < Q; q++)
@@ -242,9 +191,7 @@ __global__ __launch_bounds__(INTERP_THREADS, 2) IF_FIR_INTERP_SINGLE_READS void 
                 buf[4 * j + r] = acc[q][r];
         }
         __syncthreads();
-#pragma unroll 1
-        for (int ns = 4; ns < INTERP_N / 4; ns *= 4)
-            ip_pass<4, true>(INTERP_N, ns, tw, lds, to_lds);
+        ip_inverse_mid(tw, lds, to_lds);
         // ---- last inverse pass: positions OVL..4095 straight to the outputs; beyond M dropped ----
         float2 *ob = out + o0;                                        // (wave-uniform base: 32-bit offsets below)
         const int pend = M - o0 < INTERP_N ? (int)(M - o0) : INTERP_N; // positions past the last output are dropped
@@ -259,30 +206,16 @@ __global__ __launch_bounds__(INTERP_THREADS, 2) IF_FIR_INTERP_SINGLE_READS void 
 template <int ROWS>
 hipError_t launch_combiner_fft_rows(const CombinerArgs &a)
 {
-    constexpr int A = INTERP_N - 64 * ROWS;
-    const int64_t nblocks = (a.M + A - 1) / A;
-    // persistent workgroups, two per CU, as the interpolator's; at least one, which writes the history
-    static std::atomic<int> cus[MAX_DEVICES];
-    if (a.device < 0 || a.device >= MAX_DEVICES)
-        return hipErrorInvalidDevice;
-    if (!cus[a.device].load())
-    {
-        hipDeviceProp_t prop;
-        const hipError_t e = hipGetDeviceProperties(&prop, a.device);
-        if (e != hipSuccess)
-            return e;
-        cus[a.device].store(prop.multiProcessorCount);
-    }
-    int64_t groups = (int64_t)cus[a.device].load() * 2;
-    if (groups > nblocks)
-        groups = nblocks > 0 ? nblocks : 1;
-    if (a.grid_limit > 0 && groups > a.grid_limit)
-        groups = a.grid_limit;
+    int64_t nblocks;
+    unsigned groups;
+    const hipError_t e = ip_fft_grid(a.device, a.M, INTERP_N - 64 * ROWS, a.grid_limit, &nblocks, &groups);
+    if (e != hipSuccess)
+        return e;
     if (a.in_i16)
-        hipLaunchKernelGGL((fir_combiner_kernel<ROWS, true>), dim3((unsigned)groups), dim3(INTERP_THREADS), 0, a.stream, a.ch, a.C,
+        hipLaunchKernelGGL((fir_combiner_kernel<ROWS, true>), dim3(groups), dim3(INTERP_THREADS), 0, a.stream, a.ch, a.C,
                            static_cast<float2 *>(a.out), a.hist, a.hist_out, a.hist_len, a.H, a.tw, a.L, a.N, a.M, nblocks, a.first_out);
     else
-        hipLaunchKernelGGL((fir_combiner_kernel<ROWS, false>), dim3((unsigned)groups), dim3(INTERP_THREADS), 0, a.stream, a.ch, a.C,
+        hipLaunchKernelGGL((fir_combiner_kernel<ROWS, false>), dim3(groups), dim3(INTERP_THREADS), 0, a.stream, a.ch, a.C,
                            static_cast<float2 *>(a.out), a.hist, a.hist_out, a.hist_len, a.H, a.tw, a.L, a.N, a.M, nblocks, a.first_out);
     return hipGetLastError();
 }

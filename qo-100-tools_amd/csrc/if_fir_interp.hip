@@ -18,7 +18,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
 #include <cmath>
 
 #include "if_fir_interp.h"
@@ -34,10 +33,8 @@ template <bool I16>
 __device__ __forceinline__ void ip_write_history(const void *__restrict__ in, const float2 *__restrict__ hist, float2 *__restrict__ hist_out,
                                                  int hist_len, int64_t N)
 {
-    if (blockIdx.x != 0 || !hist_out)
-        return;
-    for (int i = threadIdx.x; i < hist_len; i += blockDim.x)
-        hist_out[i] = ip_load<I16>(in, hist, hist_len, N, N - hist_len + i);
+    if (blockIdx.x == 0 && hist_out)
+        ip_history<I16>(in, hist, hist_out, hist_len, N);
 }
 
 #if !defined(IF_FIR_INTERP_ROWS) // ================= host side + the generic kernel =================
@@ -110,40 +107,7 @@ __global__ __launch_bounds__(INTERP_THREADS) void fir_interp_generic_kernel(cons
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride)
     {
-        // output i of the call has phase i mod L (every call starts on a multiple of L); tap k meets input (i - k) / L
-        // (partial sums of 32 taps added into the total with a compensated (two-sum) addition: one running float32 sum over
-        // 3000 taps drifts past the SPEC tolerance)
-        float ar = 0.f, ai = 0.f, cr = 0.f, ci = 0.f;
-        int k = (int)(i % L);
-        while (k < T)
-        {
-            float pr = 0.f, pi = 0.f;
-            for (int c = 0; c < 32 && k < T; c++, k += L)
-            {
-                const float2 x = ip_load<I16>(in, hist, hist_len, N, (i - k) / L);
-                if constexpr (CT)
-                {
-                    const float hr = taps[2 * k], hi = taps[2 * k + 1];
-                    pr = fmaf(hr, x.x, fmaf(-hi, x.y, pr));
-                    pi = fmaf(hr, x.y, fmaf(hi, x.x, pi));
-                }
-                else
-                {
-                    const float h = taps[k];
-                    pr = fmaf(h, x.x, pr);
-                    pi = fmaf(h, x.y, pi);
-                }
-            }
-            const float sr = ar + pr, si = ai + pi;
-            const float br = sr - ar, bi = si - ai;
-            cr += (ar - (sr - br)) + (pr - br);
-            ci += (ai - (si - bi)) + (pi - bi);
-            ar = sr;
-            ai = si;
-        }
-        ar += cr;
-        ai += ci;
-        float2 y = make_float2(ar, ai);
+        float2 y = ip_phase_sum<I16, CT>(in, hist, hist_len, taps, T, L, N, i);
         if constexpr (NCO)
             y = ip_cmul(y, nco_phasor(nco_phi0 + nco_word * (uint32_t)i));
         out[i] = y;
@@ -153,14 +117,8 @@ __global__ __launch_bounds__(INTERP_THREADS) void fir_interp_generic_kernel(cons
 template <bool I16, bool CT, bool NCO>
 static hipError_t launch_generic_t(const InterpArgs &a)
 {
-    int64_t groups = (a.M + INTERP_THREADS - 1) / INTERP_THREADS;
-    if (groups < 1)
-        groups = 1; // (the history is written even by a call without outputs)
-    if (groups > 65536)
-        groups = 65536;
-    if (a.grid_limit > 0 && groups > a.grid_limit)
-        groups = a.grid_limit;
-    hipLaunchKernelGGL((fir_interp_generic_kernel<I16, CT, NCO>), dim3((unsigned)groups), dim3(INTERP_THREADS), 0, a.stream, a.in,
+    const unsigned groups = stream_generic_groups(a.M, INTERP_THREADS, a.grid_limit);
+    hipLaunchKernelGGL((fir_interp_generic_kernel<I16, CT, NCO>), dim3(groups), dim3(INTERP_THREADS), 0, a.stream, a.in,
                        static_cast<float2 *>(a.out), a.hist, a.hist_out, a.hist_len, a.taps, a.T, a.L, a.N, a.M, a.nco_word,
                        a.nco_phi0);
     return hipGetLastError();
@@ -184,7 +142,7 @@ hipError_t launch_interp_generic(const InterpArgs &a)
 
 // (single ds_read_b64 LDS reads, like the decimator's overlap-save units)
 template <int OVL_ROWS, bool I16, bool NCO, bool SMALL>
-__global__ __launch_bounds__(INTERP_THREADS, 2) IF_FIR_INTERP_SINGLE_READS void fir_interp_kernel(
+__global__ __launch_bounds__(INTERP_THREADS, 2) IF_FIR_SINGLE_READS void fir_interp_kernel(
     const void *__restrict__ in, float2 *__restrict__ out, const float2 *__restrict__ hist, float2 *__restrict__ hist_out, int hist_len,
     const float2 *__restrict__ H, const float2 *__restrict__ tw, int L, int64_t N, int64_t M, int64_t nblocks, uint32_t nco_word,
     uint32_t nco_phi0)
@@ -211,6 +169,8 @@ __global__ __launch_bounds__(INTERP_THREADS, 2) IF_FIR_INTERP_SINGLE_READS void 
                 buf[p] = (p & (L - 1)) == 0 ? ip_load<I16>(in, hist, hist_len, N, j0 + p / L) : make_float2(0.f, 0.f);
         }
         __syncthreads();
+        // (ip_forward of if_fir_interp_dev.h written out: through the function the small form's kernels compile differently and
+        // measured 0.4 - 1.2 % slower at L = 4, 8, 16 -- profiles/r11_stream_dev_ab.txt)
         int ns = 1;
         if (nf & 0x2aaa) // log2(nf) odd: one radix-2 pass first
         {
@@ -223,9 +183,7 @@ __global__ __launch_bounds__(INTERP_THREADS, 2) IF_FIR_INTERP_SINGLE_READS void 
         // ---- Z = H X (X read modulo nf), fused into the first inverse pass; 1/4096 is in H ----
         auto zsrc = [&](int k) -> float2 { return ip_cmul(H[(unsigned)k], buf[k & (nf - 1)]); };
         ip_pass<4, true>(INTERP_N, 1, tw, zsrc, to_lds);
-#pragma unroll 1
-        for (ns = 4; ns < INTERP_N / 4; ns *= 4)
-            ip_pass<4, true>(INTERP_N, ns, tw, lds, to_lds);
+        ip_inverse_mid(tw, lds, to_lds);
         // ---- last inverse pass: positions OVL..4095 straight to the outputs (rotated by the NCO); beyond M dropped ----
         float2 *ob = out + o0;                                  // (wave-uniform base: 32-bit offsets below)
         const int pend = M - o0 < INTERP_N ? (int)(M - o0) : INTERP_N; // positions past the last output are dropped
@@ -243,9 +201,9 @@ __global__ __launch_bounds__(INTERP_THREADS, 2) IF_FIR_INTERP_SINGLE_READS void 
 }
 
 template <int ROWS, bool I16, bool NCO, bool SMALL>
-static hipError_t launch_t(const InterpArgs &a, int64_t nblocks, int groups)
+static hipError_t launch_t(const InterpArgs &a, int64_t nblocks, unsigned groups)
 {
-    hipLaunchKernelGGL((fir_interp_kernel<ROWS, I16, NCO, SMALL>), dim3((unsigned)groups), dim3(INTERP_THREADS), 0, a.stream, a.in,
+    hipLaunchKernelGGL((fir_interp_kernel<ROWS, I16, NCO, SMALL>), dim3(groups), dim3(INTERP_THREADS), 0, a.stream, a.in,
                        static_cast<float2 *>(a.out), a.hist, a.hist_out, a.hist_len, a.H, a.tw, a.L, a.N, a.M, nblocks, a.nco_word,
                        a.nco_phi0);
     return hipGetLastError();
@@ -254,28 +212,13 @@ static hipError_t launch_t(const InterpArgs &a, int64_t nblocks, int groups)
 template <int ROWS>
 hipError_t launch_interp_fft_rows(const InterpArgs &a)
 {
-    constexpr int A = INTERP_N - 64 * ROWS;
-    const int64_t nblocks = (a.M + A - 1) / A;
-    // persistent workgroups, two per CU (up to 256 VGPRs per lane: two waves per SIMD); at least one, which writes the history
-    static std::atomic<int> cus[MAX_DEVICES];
-    if (a.device < 0 || a.device >= MAX_DEVICES)
-        return hipErrorInvalidDevice;
-    if (!cus[a.device].load())
-    {
-        hipDeviceProp_t prop;
-        const hipError_t e = hipGetDeviceProperties(&prop, a.device);
-        if (e != hipSuccess)
-            return e;
-        cus[a.device].store(prop.multiProcessorCount);
-    }
-    int64_t groups = (int64_t)cus[a.device].load() * 2;
-    if (groups > nblocks)
-        groups = nblocks > 0 ? nblocks : 1;
-    if (a.grid_limit > 0 && groups > a.grid_limit)
-        groups = a.grid_limit;
+    int64_t nblocks;
+    unsigned g;
+    const hipError_t e = ip_fft_grid(a.device, a.M, INTERP_N - 64 * ROWS, a.grid_limit, &nblocks, &g);
+    if (e != hipSuccess)
+        return e;
     const bool small = !a.full && a.L >= 4;
     const bool nco = a.nco_word != 0;
-    const int g = (int)groups;
 #define IP_LAUNCH(I16, NCO)                                                                                              \
     return small ? launch_t<ROWS, I16, NCO, true>(a, nblocks, g) : launch_t<ROWS, I16, NCO, false>(a, nblocks, g)
     if (a.in_i16)

@@ -1,19 +1,15 @@
-// if_fir_interp_dev.h — device code the interpolator (if_fir_interp.hip) and the channel combiner (if_fir_combiner.hip) share:
-// the sample loads, the radix-2 / radix-4 butterflies and the Stockham pass over an LDS block of up to 4096 points.  (The NCO
-// phasor nco_phasor() is in if_fir_kernels.h.)  Index algebra of the passes: tools/fft_model.py (stockham, interp_block).
+// if_fir_interp_dev.h — what the interpolator (if_fir_interp.hip) and the channel combiner (if_fir_combiner.hip) share: the
+// sample load, the history writer, the generic kernels' tap sum of one channel, the radix-2 / radix-4 butterflies, the Stockham
+// pass over an LDS block of up to 4096 points with the pass sequences of a block, and the grid of an overlap-save launch.  (What
+// every streaming family shares is in if_fir_stream_dev.h, the NCO phasor nco_phasor() in if_fir_kernels.h.)  Index algebra of
+// the passes: tools/fft_model.py (stockham, interp_block).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "if_fir_interp.h"
-
-// LDS reads as single ds_read_b64, as in the decimator's overlap-save units (if_fir_fft_dev.h, IF_FIR_LDS_SINGLE_READS): the
-// machine-level pairing is switched off per kernel here, the IR-level vectorizer for the whole unit (csrc/Makefile, NOPAIR)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define IF_FIR_INTERP_SINGLE_READS __attribute__((target("no-load-store-opt")))
-#else
-#define IF_FIR_INTERP_SINGLE_READS
-#endif
+#include "if_fir_kernels.h"
+#include "if_fir_stream_dev.h"
 
 namespace if_fir
 {
@@ -31,6 +27,8 @@ __device__ __forceinline__ float2 ip_cvt_i16(int w)
 }
 
 // input sample j of this call (float32): j < 0 from the history (hist[hist_len + j]), j >= N reads 0
+// (not stream_load of if_fir_stream_dev.h: the two forms, early returns here and one assignment there, compile to different code
+// in every kernel that uses them, and neither change has been timed -- DESIGN.md §3.11, Device side)
 template <bool I16>
 __device__ __forceinline__ float2 ip_load(const void *__restrict__ in, const float2 *__restrict__ hist, int hist_len, int64_t N,
                                           int64_t j)
@@ -43,6 +41,49 @@ __device__ __forceinline__ float2 ip_load(const void *__restrict__ in, const flo
         return ip_cvt_i16(static_cast<const int *>(in)[j]);
     else
         return static_cast<const float2 *>(in)[j];
+}
+
+// one channel's next history = the last hist_len samples of (history || input), converted to float32
+template <bool I16>
+__device__ __forceinline__ void ip_history(const void *__restrict__ in, const float2 *__restrict__ hist, float2 *__restrict__ hist_out,
+                                           int hist_len, int64_t N)
+{
+    for (int i = threadIdx.x; i < hist_len; i += blockDim.x)
+        hist_out[i] = ip_load<I16>(in, hist, hist_len, N, N - hist_len + i);
+}
+
+// the generic kernels' sum for output i of one channel: the call's output i has phase i mod L (every call starts on a multiple of
+// L), tap k meets input (i - k) / L.  Partial sums of 32 taps added into the total with a compensated (two-sum) addition: one
+// running float32 sum over 3000 taps drifts past the SPEC tolerance.
+template <bool I16, bool CT>
+__device__ __forceinline__ float2 ip_phase_sum(const void *__restrict__ in, const float2 *__restrict__ hist, int hist_len,
+                                               const float *__restrict__ taps, int T, int L, int64_t N, int64_t i)
+{
+    float ar = 0.f, ai = 0.f, cr = 0.f, ci = 0.f;
+    int k = (int)(i % L);
+    while (k < T)
+    {
+        float pr = 0.f, pi = 0.f;
+        for (int c = 0; c < 32 && k < T; c++, k += L)
+        {
+            const float2 x = ip_load<I16>(in, hist, hist_len, N, (i - k) / L);
+            if constexpr (CT)
+            {
+                const float hr = taps[2 * k], hi = taps[2 * k + 1];
+                pr = fmaf(hr, x.x, fmaf(-hi, x.y, pr));
+                pi = fmaf(hr, x.y, fmaf(hi, x.x, pi));
+            }
+            else
+            {
+                const float h = taps[k];
+                pr = fmaf(h, x.x, pr);
+                pi = fmaf(h, x.y, pi);
+            }
+        }
+        two_sum_add(ar, cr, pr);
+        two_sum_add(ai, ci, pi);
+    }
+    return make_float2(ar + cr, ai + ci);
 }
 
 // radix-R butterfly; forward = exp(-j ...), INV = exp(+j ...)
@@ -112,6 +153,46 @@ __device__ __forceinline__ void ip_pass(int nf, int ns, const float2 *__restrict
         }
     }
     __syncthreads();
+}
+
+// the forward transform of nf points in place: one radix-2 pass first when log2(nf) is odd, then radix-4 passes.  (The combiner
+// calls it; fir_interp_kernel has the same lines written out, because through this function its small form compiled to slower
+// code: DESIGN.md §3.11, Device side.)
+template <class Src, class Dst>
+__device__ __forceinline__ void ip_forward(int nf, const float2 *__restrict__ tw, Src src, Dst dst)
+{
+    int ns = 1;
+    if (nf & 0x2aaa)
+    {
+        ip_pass<2, false>(nf, ns, tw, src, dst);
+        ns = 2;
+    }
+#pragma unroll 1
+    for (; ns < nf; ns *= 4)
+        ip_pass<4, false>(nf, ns, tw, src, dst);
+}
+
+// the 4096-point inverse's middle passes, ns = 4 .. 256 (the first one takes the product with H, the last one stores the outputs)
+template <class Src, class Dst>
+__device__ __forceinline__ void ip_inverse_mid(const float2 *__restrict__ tw, Src src, Dst dst)
+{
+#pragma unroll 1
+    for (int ns = 4; ns < INTERP_N / 4; ns *= 4)
+        ip_pass<4, true>(INTERP_N, ns, tw, src, dst);
+}
+
+// an overlap-save launch over M outputs in blocks that keep A of them: persistent workgroups, two per CU (up to 256 VGPRs per
+// lane: two waves per SIMD); at least one, which writes the history.  (The kernels use static LDS: nothing to set per kernel.)
+inline hipError_t ip_fft_grid(int device, int64_t M, int A, int grid_limit, int64_t *nblocks, unsigned *groups)
+{
+    static DeviceSetup setup;
+    int cus = 0;
+    const hipError_t e = device_setup(setup, device, nullptr, 0, &cus);
+    if (e != hipSuccess)
+        return e;
+    *nblocks = (M + A - 1) / A;
+    *groups = stream_persistent_groups(cus, 2, *nblocks, grid_limit);
+    return hipSuccess;
 }
 
 } // namespace if_fir

@@ -100,7 +100,8 @@ struct DeviceSetup
     bool done[MAX_DEVICES] = {};
     int cus[MAX_DEVICES] = {};
 };
-// `kern` gets its dynamic-LDS limit raised to lds_bytes once per device; *cus (optional) = CU count of the device
+// `kern` (nullptr: a kernel with static LDS only, nothing to set) gets its dynamic-LDS limit raised to lds_bytes once per
+// device; *cus (optional) = CU count of the device
 inline hipError_t device_setup(DeviceSetup &d, int device, const void *kern, int lds_bytes, int *cus)
 {
     if (device < 0 || device >= MAX_DEVICES)
@@ -108,7 +109,7 @@ inline hipError_t device_setup(DeviceSetup &d, int device, const void *kern, int
     std::lock_guard<std::mutex> lock(d.mu);
     if (!d.done[device])
     {
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        hipError_t e = kern ? hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) : hipSuccess;
         if (e != hipSuccess)
             return e;
         hipDeviceProp_t prop;

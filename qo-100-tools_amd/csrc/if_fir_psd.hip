@@ -19,63 +19,29 @@
 
 #include "if_fir_kernels.h"
 #include "if_fir_psd.h"
+#include "if_fir_stream_dev.h"
 
 namespace if_fir
 {
 
-typedef float psd_v2f __attribute__((ext_vector_type(2)));
-
-// sample j of this call as float32 (I, Q): j < 0 from the carried buffer (carry[carried + j]); outside both reads 0
-template <bool I16>
-__device__ __forceinline__ psd_v2f psd_load(const void *__restrict__ in, const float2 *__restrict__ carry, int64_t carried, int64_t n,
-                                            int64_t j)
+__device__ __forceinline__ stream_v2f psd_cmul(const stream_v2f a, const stream_v2f w)
 {
-    psd_v2f v = {0.f, 0.f};
-    if (j < 0)
-    {
-        if (j + carried >= 0)
-        {
-            const float2 h = carry[j + carried];
-            v.x = h.x;
-            v.y = h.y;
-        }
-    }
-    else if (j < n)
-    {
-        if constexpr (I16)
-        {
-            const int w = static_cast<const int *>(in)[j];
-            v.x = (float)(short)(w & 0xffff) * (1.0f / 32768.0f);
-            v.y = (float)(w >> 16) * (1.0f / 32768.0f);
-        }
-        else
-        {
-            const float2 s = static_cast<const float2 *>(in)[j];
-            v.x = s.x;
-            v.y = s.y;
-        }
-    }
-    return v;
-}
-
-__device__ __forceinline__ psd_v2f psd_cmul(const psd_v2f a, const psd_v2f w)
-{
-    return psd_v2f{fmaf(a.x, w.x, -a.y * w.y), fmaf(a.x, w.y, a.y * w.x)};
+    return stream_v2f{fmaf(a.x, w.x, -a.y * w.y), fmaf(a.x, w.y, a.y * w.x)};
 }
 
 // one in-place radix-4 decimation-in-frequency pass over sub-blocks of LEN: butterfly j of a sub-block reads and writes the
 // same four places j, j + LEN/4, j + LEN/2, j + 3 LEN/4, so passes only need a barrier between them
 template <int N, int LEN>
-__device__ __forceinline__ void psd_pass4(psd_v2f *__restrict__ x, const psd_v2f *__restrict__ tw, int tid)
+__device__ __forceinline__ void psd_pass4(stream_v2f *__restrict__ x, const stream_v2f *__restrict__ tw, int tid)
 {
     constexpr int Q = LEN / 4, STEP = N / LEN;
     for (int b = tid; b < N / 4; b += PSD_THREADS)
     {
         const int j = b % Q, base = (b / Q) * LEN + j;
-        const psd_v2f a0 = x[base], a1 = x[base + Q], a2 = x[base + 2 * Q], a3 = x[base + 3 * Q];
-        const psd_v2f t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3, d = a1 - a3;
-        const psd_v2f t3 = {d.y, -d.x}; // -i (a1 - a3)
-        psd_v2f y0 = t0 + t2, y1 = t1 + t3, y2 = t0 - t2, y3 = t1 - t3;
+        const stream_v2f a0 = x[base], a1 = x[base + Q], a2 = x[base + 2 * Q], a3 = x[base + 3 * Q];
+        const stream_v2f t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3, d = a1 - a3;
+        const stream_v2f t3 = {d.y, -d.x}; // -i (a1 - a3)
+        stream_v2f y0 = t0 + t2, y1 = t1 + t3, y2 = t0 - t2, y3 = t1 - t3;
         if constexpr (Q > 1)
         {
             y1 = psd_cmul(y1, tw[j * STEP]);
@@ -90,7 +56,7 @@ __device__ __forceinline__ void psd_pass4(psd_v2f *__restrict__ x, const psd_v2f
 }
 
 template <int N, int LEN>
-__device__ __forceinline__ void psd_passes(psd_v2f *__restrict__ x, const psd_v2f *__restrict__ tw, int tid)
+__device__ __forceinline__ void psd_passes(stream_v2f *__restrict__ x, const stream_v2f *__restrict__ tw, int tid)
 {
     if constexpr (LEN >= 4)
     {
@@ -102,7 +68,7 @@ __device__ __forceinline__ void psd_passes(psd_v2f *__restrict__ x, const psd_v2
     {
         for (int b = tid; b < N / 2; b += PSD_THREADS)
         {
-            const psd_v2f a0 = x[2 * b], a1 = x[2 * b + 1];
+            const stream_v2f a0 = x[2 * b], a1 = x[2 * b + 1];
             x[2 * b] = a0 + a1;
             x[2 * b + 1] = a0 - a1;
         }
@@ -119,8 +85,8 @@ __global__ __launch_bounds__(PSD_THREADS) void psd_chunk_kernel(const void *__re
 {
     constexpr int R = N / PSD_THREADS; // samples, and at most bins, per lane
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    psd_v2f *x = reinterpret_cast<psd_v2f *>(smem);
-    psd_v2f *tw = x + N;
+    stream_v2f *x = reinterpret_cast<stream_v2f *>(smem);
+    stream_v2f *tw = x + N;
     const int tid = threadIdx.x;
     float w[R];
     int where[R];
@@ -129,7 +95,7 @@ __global__ __launch_bounds__(PSD_THREADS) void psd_chunk_kernel(const void *__re
     {
         const int e = tid + i * PSD_THREADS;
         const float2 t = twiddle[e];
-        tw[e] = psd_v2f{t.x, t.y};
+        tw[e] = stream_v2f{t.x, t.y};
         w[i] = window[e];
         where[i] = e < bins ? (int)bin_pos[e] : 0;
     }
@@ -150,14 +116,14 @@ __global__ __launch_bounds__(PSD_THREADS) void psd_chunk_kernel(const void *__re
             for (int i = 0; i < R; i++)
             {
                 const int e = tid + i * PSD_THREADS;
-                x[e] = psd_load<I16>(in, carry, carried, n, first + e) * w[i];
+                x[e] = stream_load<I16>(in, carry, carried, n, first + e) * w[i];
             }
             __syncthreads();
             psd_passes<N, N>(x, tw, tid);
 #pragma unroll
             for (int i = 0; i < R; i++)
             {
-                const psd_v2f v = x[where[i]];
+                const stream_v2f v = x[where[i]];
                 sum[i] += fmaf(v.x, v.x, v.y * v.y);
             }
         }
@@ -216,7 +182,7 @@ __global__ __launch_bounds__(PSD_THREADS) void psd_carry_kernel(const void *__re
     // the last `keep` samples of (carried || call)
     for (int64_t i = (int64_t)blockIdx.x * PSD_THREADS + threadIdx.x; i < keep; i += (int64_t)gridDim.x * PSD_THREADS)
     {
-        const psd_v2f v = psd_load<I16>(in, carry, carried, n, n - keep + i);
+        const stream_v2f v = stream_load<I16>(in, carry, carried, n, n - keep + i);
         carry_out[i] = make_float2(v.x, v.y);
     }
 }
@@ -231,10 +197,9 @@ static hipError_t launch_chunks(const PsdArgs &a)
     if (e != hipSuccess)
         return e;
     // a grid-stride loop over the chunks; the twiddles are staged once per workgroup, 160 KiB of LDS hold 160 / (16 N / 1024) of them
-    int64_t groups = (int64_t)cus * (N >= 4096 ? 2 : N >= 2048 ? 4 : 8);
-    if (groups > (int64_t)a.plan.chunks)
-        groups = (int64_t)a.plan.chunks;
-    hipLaunchKernelGGL((psd_chunk_kernel<N, I16>), dim3((unsigned)groups), dim3(PSD_THREADS), lds, a.stream, a.in, a.carry, a.window,
+    // (the caller launches only with chunks > 0, and there is no grid limit: at most one workgroup per chunk)
+    const unsigned groups = stream_persistent_groups(cus, N >= 4096 ? 2 : N >= 2048 ? 4 : 8, (int64_t)a.plan.chunks, 0);
+    hipLaunchKernelGGL((psd_chunk_kernel<N, I16>), dim3(groups), dim3(PSD_THREADS), lds, a.stream, a.in, a.carry, a.window,
                        a.twiddle, a.bin_pos, a.work, a.H, a.K, a.bins, a.plan.chunk0, (uint32_t)a.plan.chunks, a.n, a.carried);
     return hipGetLastError();
 }

@@ -19,99 +19,57 @@
 
 #include "if_fir_kernels.h"
 #include "if_fir_resamp.h"
+#include "if_fir_stream_dev.h"
 
 namespace if_fir
 {
 
-typedef float rs_v2f __attribute__((ext_vector_type(2)));
-
-// LDS reads as single ds_read_b64 / ds_read_b32, as in the overlap-save units (a ds_read2_b64 pair takes 8 LDS cycles on 32 banks,
-// two single reads 2 each on 64): the machine-level pairing is switched off per kernel here, the IR-level vectorizer for the
-// whole unit (csrc/Makefile, NOPAIR).  The inner loop is bound by its LDS reads, so this is the kernel's rate.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define IF_FIR_RESAMP_SINGLE_READS __attribute__((target("no-load-store-opt")))
-#else
-#define IF_FIR_RESAMP_SINGLE_READS
-#endif
-
-// input sample j of this call as float32 (I, Q): j < 0 from the history (hist[hist_len + j]), j >= N reads 0
-template <bool I16>
-__device__ __forceinline__ rs_v2f rs_load(const void *__restrict__ in, const float2 *__restrict__ hist, int hist_len, int64_t N,
-                                          int64_t j)
-{
-    rs_v2f v = {0.f, 0.f};
-    if (j < 0)
-    {
-        if (j + hist_len >= 0)
-        {
-            const float2 h = hist[j + hist_len];
-            v.x = h.x;
-            v.y = h.y;
-        }
-    }
-    else if (j < N)
-    {
-        if constexpr (I16)
-        {
-            const int w = static_cast<const int *>(in)[j];
-            v.x = (float)(short)(w & 0xffff) * (1.0f / 32768.0f);
-            v.y = (float)(w >> 16) * (1.0f / 32768.0f);
-        }
-        else
-        {
-            const float2 s = static_cast<const float2 *>(in)[j];
-            v.x = s.x;
-            v.y = s.y;
-        }
-    }
-    return v;
-}
-
 // one tap on RESAMP_R outputs: real h -> one packed FMA each; complex (hr, hi) -> SPEC §3's generic complex formula,
 // re = fma(-xi, hi, fma(xr, hr, re)), im = fma(xi, hr, fma(xr, hi, im)), as two packed FMAs
 template <bool CT, typename TAP>
-__device__ __forceinline__ void rs_tap(const TAP h, const rs_v2f *__restrict__ xs, const int (&x0)[RESAMP_R], int e,
-                                       rs_v2f (&seg)[RESAMP_R])
+__device__ __forceinline__ void rs_tap(const TAP h, const stream_v2f *__restrict__ xs, const int (&x0)[RESAMP_R], int e,
+                                       stream_v2f (&seg)[RESAMP_R])
 {
 #pragma unroll
     for (int k = 0; k < RESAMP_R; k++)
     {
-        const rs_v2f x = xs[x0[k] + e];
+        const stream_v2f x = xs[x0[k] + e];
         if constexpr (CT)
         {
-            const rs_v2f xr = {x.x, x.x}, xi = {-x.y, x.y}, hs = {h.y, h.x};
+            const stream_v2f xr = {x.x, x.x}, xi = {-x.y, x.y}, hs = {h.y, h.x};
             seg[k] = __builtin_elementwise_fma(xr, h, seg[k]);
             seg[k] = __builtin_elementwise_fma(xi, hs, seg[k]);
         }
         else
         {
-            const rs_v2f hh = {h, h};
+            const stream_v2f hh = {h, h};
             seg[k] = __builtin_elementwise_fma(hh, x, seg[k]);
         }
     }
 }
 
+// (single LDS reads, if_fir_stream_dev.h: the inner loop is bound by its LDS reads, so this is the kernel's rate)
 template <bool I16, bool CT>
-__global__ __launch_bounds__(RESAMP_THREADS) IF_FIR_RESAMP_SINGLE_READS void fir_resamp_kernel(const void *__restrict__ in, float2 *__restrict__ out,
+__global__ __launch_bounds__(RESAMP_THREADS) IF_FIR_SINGLE_READS void fir_resamp_kernel(const void *__restrict__ in, float2 *__restrict__ out,
                                                                    const float2 *__restrict__ hist, float2 *__restrict__ hist_out,
                                                                    const float *__restrict__ taps, int L, int M, int K, int KP, int B,
                                                                    int t0, int64_t N, int64_t count, int64_t ntiles)
 {
-    using tap_t = typename std::conditional<CT, rs_v2f, float>::type;
+    using tap_t = typename std::conditional<CT, stream_v2f, float>::type;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int hist_len = K - 1;
     if (blockIdx.x == 0)
         for (int i = tid; i < hist_len; i += RESAMP_THREADS)
         {
-            const rs_v2f v = rs_load<I16>(in, hist, hist_len, N, N - hist_len + i);
+            const stream_v2f v = stream_load<I16>(in, hist, hist_len, N, N - hist_len + i);
             hist_out[i] = make_float2(v.x, v.y);
         }
     if ((int64_t)blockIdx.x >= ntiles)
         return; // (uniform per workgroup: a call without outputs only moves the history)
     const int tap_entries = L * KP;
     tap_t *tl = reinterpret_cast<tap_t *>(smem);
-    rs_v2f *xs = reinterpret_cast<rs_v2f *>(smem + (((size_t)tap_entries * sizeof(tap_t) + 7) & ~(size_t)7));
+    stream_v2f *xs = reinterpret_cast<stream_v2f *>(smem + (((size_t)tap_entries * sizeof(tap_t) + 7) & ~(size_t)7));
     for (int i = tid; i < tap_entries; i += RESAMP_THREADS)
         tl[i] = reinterpret_cast<const tap_t *>(taps)[i];
 
@@ -137,23 +95,23 @@ __global__ __launch_bounds__(RESAMP_THREADS) IF_FIR_RESAMP_SINGLE_READS void fir
         __syncthreads(); // the previous tile has been read
         const int64_t first = tile * tile_in - (K - 1);
         for (int s = tid; s < x_len; s += RESAMP_THREADS)
-            xs[s] = rs_load<I16>(in, hist, hist_len, N, first + s);
+            xs[s] = stream_load<I16>(in, hist, hist_len, N, first + s);
         __syncthreads();
 
         // the total and what its additions lost (two-sum): plain adds of 32-tap segments left 1.01e-6 of the peak on 1023 complex
         // phase taps, past SPEC §3's bound (docs/SPEC.md §7)
-        rs_v2f acc[RESAMP_R], lost[RESAMP_R];
+        stream_v2f acc[RESAMP_R], lost[RESAMP_R];
 #pragma unroll
         for (int k = 0; k < RESAMP_R; k++)
-            acc[k] = lost[k] = rs_v2f{0.f, 0.f};
+            acc[k] = lost[k] = stream_v2f{0.f, 0.f};
         // e = K - 1 - j counts up from the oldest sample while j walks down through the segments
         int e = 0;
         for (int len = top; e < K; len = RESAMP_SEG)
         {
-            rs_v2f seg[RESAMP_R];
+            stream_v2f seg[RESAMP_R];
 #pragma unroll
             for (int k = 0; k < RESAMP_R; k++)
-                seg[k] = rs_v2f{0.f, 0.f};
+                seg[k] = stream_v2f{0.f, 0.f};
             const int end = e + len;
             for (; e + 8 <= end; e += 8)
             {
@@ -165,11 +123,7 @@ __global__ __launch_bounds__(RESAMP_THREADS) IF_FIR_RESAMP_SINGLE_READS void fir
                 rs_tap<CT>(row[K - 1 - e], xs, x0, e, seg);
 #pragma unroll
             for (int k = 0; k < RESAMP_R; k++)
-            {
-                const rs_v2f sum = acc[k] + seg[k], b = sum - acc[k];
-                lost[k] += (acc[k] - (sum - b)) + (seg[k] - b);
-                acc[k] = sum;
-            }
+                two_sum_add(acc[k], lost[k], seg[k]);
         }
 #pragma unroll
         for (int k = 0; k < RESAMP_R; k++)
@@ -197,12 +151,8 @@ static hipError_t launch_t(const ResampArgs &a)
     const int64_t ntiles = (a.count + s.tile_out - 1) / s.tile_out;
     // a grid-stride loop over the tiles on at most 8 workgroups per CU (more gain nothing: the tap table is staged once per
     // workgroup); at least one, which writes the history
-    int64_t groups = (int64_t)cus * 8;
-    if (groups > ntiles)
-        groups = ntiles > 0 ? ntiles : 1;
-    if (a.grid_limit > 0 && groups > a.grid_limit)
-        groups = a.grid_limit;
-    hipLaunchKernelGGL((fir_resamp_kernel<I16, CT>), dim3((unsigned)groups), dim3(RESAMP_THREADS), resamp_lds_bytes(s, a.ctaps), a.stream,
+    const unsigned groups = stream_persistent_groups(cus, 8, ntiles, a.grid_limit);
+    hipLaunchKernelGGL((fir_resamp_kernel<I16, CT>), dim3(groups), dim3(RESAMP_THREADS), resamp_lds_bytes(s, a.ctaps), a.stream,
                        a.in, static_cast<float2 *>(a.out), a.hist, a.hist_out, a.taps, a.L, a.M, s.K, s.KP, s.B, a.t0, a.N, a.count, ntiles);
     return hipGetLastError();
 }

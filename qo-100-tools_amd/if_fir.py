@@ -255,6 +255,16 @@ def _f32p(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
 
+def _taps_arg(taps, complex_taps):
+    """(contiguous float32 array -- complex taps interleaved (re, im) --, tap count, complex flag) of a constructor's taps"""
+    taps = np.asarray(taps)
+    if np.iscomplexobj(taps):
+        taps = np.ascontiguousarray(taps.astype(np.complex64)).view(np.float32)
+        complex_taps = True
+    taps = np.ascontiguousarray(taps, dtype=np.float32)
+    return taps, (taps.size // 2 if complex_taps else taps.size), bool(complex_taps)
+
+
 def bpf_design(taps, f_low=0.15, f_high=0.25, window=WINDOW_BLACKMAN):
     """if_bpf_design(): windowed-sinc band-pass taps (float32)."""
     h = np.zeros(max(int(taps), 0), dtype=np.float32)
@@ -279,21 +289,12 @@ class IfFir:
         # lib_path (development tools only, tools/ab_inproc.py): another build of the development library, loaded beside the
         # default one so that two builds can be timed alternately in one process
         self._L = _load(os.path.abspath(lib_path), True) if lib_path else dev_lib() if dev else lib()
-        taps = np.asarray(taps)
-        if np.iscomplexobj(taps):
-            taps = np.ascontiguousarray(taps.astype(np.complex64)).view(np.float32)
-            complex_taps = True
-        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        taps, count, complex_taps = _taps_arg(taps, complex_taps)
         self._ctx = ctypes.c_void_p()
         self.taps = taps
         self.decimation = int(decimation)
-        if complex_taps:
-            ok = self._L.if_fir_init_complex(ctypes.byref(self._ctx), _f32p(taps), taps.size // 2, self.decimation,
-                                           int(max_samples), int(device))
-        else:
-            ok = self._L.if_fir_init(ctypes.byref(self._ctx), _f32p(taps), taps.size, self.decimation,
-                                   int(max_samples), int(device))
-        if not ok:
+        init = self._L.if_fir_init_complex if complex_taps else self._L.if_fir_init
+        if not init(ctypes.byref(self._ctx), _f32p(taps), count, self.decimation, int(max_samples), int(device)):
             self._ctx = ctypes.c_void_p()
             raise IfFirError(self._L.if_fir_last_error(None).decode())
         if backend is not None:
@@ -535,6 +536,24 @@ class _StreamCtx:
             iq = np.ascontiguousarray(iq, dtype=np.float32).reshape(-1)
         return iq, iq.size // 2
 
+    def _process(self, iq):
+        """<prefix>process() of a family with one input and one output stream: host array in, interleaved float32 out"""
+        iq, n = self._host_input(iq)
+        out = np.empty(2 * self.out_count(n), dtype=np.float32)
+        m = ctypes.c_uint64(0)
+        dummy = np.zeros(2, dtype=np.float32)
+        self._check(self._c("process")(self._ctx, ctypes.c_void_p(iq.ctypes.data if n else dummy.ctypes.data),
+                                       _f32p(out if out.size else dummy), n, ctypes.byref(m)))
+        assert m.value * 2 == out.size
+        return out
+
+    def _process_device(self, dev_in, dev_out, samples):
+        """<prefix>process_device() of such a family: raw device pointers (ints), asynchronous; the output sample count"""
+        m = ctypes.c_uint64(0)
+        self._check(self._c("process_device")(self._ctx, ctypes.c_void_p(dev_in), ctypes.c_void_p(dev_out), int(samples),
+                                              ctypes.byref(m)))
+        return int(m.value)
+
 
 class IfFirInterp(_StreamCtx):
     """One if_fir_interp_t: upsample by `interpolation`, filter, optionally mix up (docs/SPEC.md §6).  Methods mirror the C
@@ -543,17 +562,13 @@ class IfFirInterp(_StreamCtx):
 
     def __init__(self, taps, interpolation, max_samples=1 << 20, device=0, backend=None, complex_taps=False, dev=False):
         self._L = dev_lib() if dev else lib()
-        taps = np.asarray(taps)
-        if np.iscomplexobj(taps):
-            taps = np.ascontiguousarray(taps.astype(np.complex64)).view(np.float32)
-            complex_taps = True
-        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        taps, count, complex_taps = _taps_arg(taps, complex_taps)
         self._ctx = ctypes.c_void_p()
         self.taps = taps
         self.interpolation = int(interpolation)
         self._i16 = False
         init = self._L.if_fir_interp_init_complex if complex_taps else self._L.if_fir_interp_init
-        if not init(ctypes.byref(self._ctx), _f32p(taps), taps.size // 2 if complex_taps else taps.size, self.interpolation,
+        if not init(ctypes.byref(self._ctx), _f32p(taps), count, self.interpolation,
                     int(max_samples), int(device)):
             self._ctx = ctypes.c_void_p()
             raise IfFirError(self._c("last_error")(None).decode())
@@ -581,21 +596,11 @@ class IfFirInterp(_StreamCtx):
     def process(self, iq):
         """if_fir_interp_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in,
         interleaved float32 out."""
-        iq, n = self._host_input(iq)
-        out = np.empty(2 * self.out_count(n), dtype=np.float32)
-        m = ctypes.c_uint64(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._L.if_fir_interp_process(self._ctx, ctypes.c_void_p(iq.ctypes.data if n else dummy.ctypes.data),
-                                                  _f32p(out if out.size else dummy), n, ctypes.byref(m)))
-        assert m.value * 2 == out.size
-        return out
+        return self._process(iq)
 
     def process_device(self, dev_in, dev_out, samples):
         """if_fir_interp_process_device(): raw device pointers (ints), asynchronous.  Returns the output sample count."""
-        m = ctypes.c_uint64(0)
-        self._check(self._L.if_fir_interp_process_device(self._ctx, ctypes.c_void_p(dev_in), ctypes.c_void_p(dev_out),
-                                                         int(samples), ctypes.byref(m)))
-        return int(m.value)
+        return self._process_device(dev_in, dev_out, samples)
 
     def debug_config(self, force_full=False, grid_limit=0):
         """if_fir_debug_interp_config() (development library: construct with dev=True)."""
@@ -634,11 +639,7 @@ class IfFirCombiner(_StreamCtx):
 
     def __init__(self, taps, interpolation, centres, max_samples=1 << 20, device=0, backend=None, complex_taps=False, dev=False):
         self._L = dev_lib() if dev else lib()
-        taps = np.asarray(taps)
-        if np.iscomplexobj(taps):
-            taps = np.ascontiguousarray(taps.astype(np.complex64)).view(np.float32)
-            complex_taps = True
-        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        taps, count, complex_taps = _taps_arg(taps, complex_taps)
         centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1)
         self._ctx = ctypes.c_void_p()
         self.taps = taps
@@ -646,7 +647,7 @@ class IfFirCombiner(_StreamCtx):
         self.channels = int(centres.size)
         self._i16 = False
         init = self._L.if_fir_combiner_init_complex if complex_taps else self._L.if_fir_combiner_init
-        if not init(ctypes.byref(self._ctx), _f32p(taps), taps.size // 2 if complex_taps else taps.size, self.interpolation,
+        if not init(ctypes.byref(self._ctx), _f32p(taps), count, self.interpolation,
                     self.channels, centres.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(max_samples), int(device)):
             self._ctx = ctypes.c_void_p()
             raise IfFirError(self._c("last_error")(None).decode())
@@ -730,18 +731,14 @@ class IfFirResamp(_StreamCtx):
 
     def __init__(self, taps, interpolation, decimation, max_samples=1 << 20, device=0, complex_taps=False, dev=False):
         self._L = dev_lib() if dev else lib()
-        taps = np.asarray(taps)
-        if np.iscomplexobj(taps):
-            taps = np.ascontiguousarray(taps.astype(np.complex64)).view(np.float32)
-            complex_taps = True
-        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        taps, count, complex_taps = _taps_arg(taps, complex_taps)
         self._ctx = ctypes.c_void_p()
         self.taps = taps
         self.interpolation, self.decimation = int(interpolation), int(decimation)
         self._i16 = False
         self._dev, self._grid_limit = bool(dev), 0
         init = self._L.if_fir_resamp_init_complex if complex_taps else self._L.if_fir_resamp_init
-        if not init(ctypes.byref(self._ctx), _f32p(taps), taps.size // 2 if complex_taps else taps.size, self.interpolation,
+        if not init(ctypes.byref(self._ctx), _f32p(taps), count, self.interpolation,
                     self.decimation, int(max_samples), int(device)):
             self._ctx = ctypes.c_void_p()
             raise IfFirError(self._c("last_error")(None).decode())
@@ -753,21 +750,11 @@ class IfFirResamp(_StreamCtx):
     def process(self, iq):
         """if_fir_resamp_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in,
         interleaved float32 out."""
-        iq, n = self._host_input(iq)
-        out = np.empty(2 * self.out_count(n), dtype=np.float32)
-        m = ctypes.c_uint64(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._L.if_fir_resamp_process(self._ctx, ctypes.c_void_p(iq.ctypes.data if n else dummy.ctypes.data),
-                                                  _f32p(out if out.size else dummy), n, ctypes.byref(m)))
-        assert m.value * 2 == out.size
-        return out
+        return self._process(iq)
 
     def process_device(self, dev_in, dev_out, samples):
         """if_fir_resamp_process_device(): raw device pointers (ints), asynchronous.  Returns the output sample count."""
-        m = ctypes.c_uint64(0)
-        self._check(self._L.if_fir_resamp_process_device(self._ctx, ctypes.c_void_p(dev_in), ctypes.c_void_p(dev_out),
-                                                         int(samples), ctypes.byref(m)))
-        return int(m.value)
+        return self._process_device(dev_in, dev_out, samples)
 
     def debug_config(self, grid_limit=0):
         """if_fir_debug_resamp_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
