@@ -394,6 +394,45 @@ uint8_t if_fir_psd_process(if_fir_psd_t *pCtx, const void *pIQIn, uint64_t ullSa
 uint8_t if_fir_psd_process_device(if_fir_psd_t *pCtx, const void *pDevIn, uint64_t ullSamples, uint16_t *pusDevBins, float *pfDevPower,
                                   uint32_t *pulFrames);
 
+/* ---- real-input down-converter (docs/SPEC.md §10; BUILD-DEFINED) -----------------------------------------------------------
+ * Real IF samples r[a] (one float32, or one int16 = value * 2^15, per sample) to decimated complex baseband in ONE pass:
+ *     x'[a] = r[a] exp(-j 2 pi ((P a) mod 2^32) / 2^32);   y[n] = sum_k h[k] x'[n-k];   y_D[m] = y[m*D]
+ * a, n = absolute index since init/reset, P = round(f * 2^32) mod 2^32 (if_fir_ddc_set_nco; P = 0: no mixing): by definition the
+ * decimator with if_fir_set_nco fed (r, 0).  D in 1..64, T <= 4096, taps real or complex.  A call whose first sample has absolute
+ * index c and which brings N samples emits the outputs with n in [c, c+N), n mod D == 0 (possibly none).
+ * process(a||b) == process(a); process(b), bit for bit, wherever the stream is cut.  Output float32 I/Q.
+ * Errors: 0 + if_fir_ddc_last_error(); a failed call leaves the context usable and its stream position unchanged.
+ * Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_ddc if_fir_ddc_t;
+
+uint8_t if_fir_ddc_init(if_fir_ddc_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulDecimation, uint64_t ullMaxSamples,
+                        int32_t lDevice);
+/* complex taps: ulTaps interleaved (re, im) pairs */
+uint8_t if_fir_ddc_init_complex(if_fir_ddc_t **ppCtx, const float *pfTapsIQ, uint32_t ulTaps, uint32_t ulDecimation,
+                                uint64_t ullMaxSamples, int32_t lDevice);
+void if_fir_ddc_destroy(if_fir_ddc_t *pCtx);
+/* zero the history and the stream position (the NCO frequency stays) */
+uint8_t if_fir_ddc_reset(if_fir_ddc_t *pCtx);
+/* IF_FIR_INPUT_F32 (4 bytes per sample) or IF_FIR_INPUT_I16 (2 bytes, value = int16 * 2^-15); the history is float32, so a
+ * change keeps the stream */
+uint8_t if_fir_ddc_set_input_format(if_fir_ddc_t *pCtx, uint32_t ulFormat);
+/* dFreq in cycles/sample, |dFreq| <= 0.5; holds from the next call as if set since the last reset (the phase is a function of
+ * the absolute index only).  Waits for the context's stream. */
+uint8_t if_fir_ddc_set_nco(if_fir_ddc_t *pCtx, double dFreq);
+/* the quantised frequency P / 2^32, P read as a signed word */
+uint8_t if_fir_ddc_get_nco(const if_fir_ddc_t *pCtx, double *pdFreq);
+uint8_t if_fir_ddc_set_stream(if_fir_ddc_t *pCtx, void *pStream);
+uint8_t if_fir_ddc_synchronize(if_fir_ddc_t *pCtx);
+const char *if_fir_ddc_last_error(const if_fir_ddc_t *pCtx);
+/* outputs of a call with ullSamples inputs at the current stream position */
+uint64_t if_fir_ddc_out_count(const if_fir_ddc_t *pCtx, uint64_t ullSamples);
+/* host pointers, synchronous; ullSamples <= ullMaxSamples of init; pfIQOut holds if_fir_ddc_out_count() samples */
+uint8_t if_fir_ddc_process(if_fir_ddc_t *pCtx, const void *pIn, float *pfIQOut, uint64_t ullSamples, uint64_t *pullOutSamples);
+/* device pointers aligned to one sample (input 4 bytes, 2 for int16; output 8 bytes), asynchronous on the context's stream;
+ * pDevOut holds if_fir_ddc_out_count() samples */
+uint8_t if_fir_ddc_process_device(if_fir_ddc_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples,
+                                  uint64_t *pullOutSamples);
+
 #ifdef __cplusplus
 }
 #endif

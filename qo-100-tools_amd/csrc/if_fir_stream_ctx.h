@@ -1,4 +1,4 @@
-// if_fir_stream_ctx.h — what the C-ABI shims of the streaming contexts (if_fir_interp_t, if_fir_resamp_t, if_fir_psd_t) share: the base
+// if_fir_stream_ctx.h — what the C-ABI shims of the streaming contexts (if_fir_interp_t, if_fir_resamp_t, if_fir_psd_t, if_fir_ddc_t) share: the base
 // of the context struct, the message writer, opening and closing, and the host-pointer ("staged") call.  Host code only.
 //
 // The rule for what belongs here: code in this header never branches on which family calls it.  Where the families differ --
@@ -169,12 +169,13 @@ static inline bool stream_ctx_fits(StreamCtx *c, const char *who, uint64_t n)
 // stream, run() the family's run_device on its staging buffers, copy_back() what that produced (a hipError_t: the asynchronous
 // copies, hipSuccess if there is nothing to copy), synchronize.  *state is the family's streaming state, the fields run_device
 // advances; what = "outputs" / "frames", for the message.
+// (stream_ctx_staged_bytes: the same for a family whose samples are not IQ pairs; it gives the bytes of its input itself)
 template <typename State, typename Run, typename CopyBack>
-static inline uint8_t stream_ctx_staged(StreamCtx *c, const char *who, const char *what, void *d_stage_in, const void *host_in,
-                                        uint64_t n, State *state, Run run, CopyBack copy_back)
+static inline uint8_t stream_ctx_staged_bytes(StreamCtx *c, const char *who, const char *what, void *d_stage_in, const void *host_in,
+                                              size_t bytes, State *state, Run run, CopyBack copy_back)
 {
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(d_stage_in, host_in, (size_t)n * (c->in_i16 ? 4 : 8), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_stage_in, host_in, bytes, hipMemcpyHostToDevice, c->stream));
     const State before = *state;
     if (!run())
     {
@@ -194,6 +195,13 @@ static inline uint8_t stream_ctx_staged(StreamCtx *c, const char *who, const cha
         return 0;
     }
     return 1;
+}
+
+template <typename State, typename Run, typename CopyBack>
+static inline uint8_t stream_ctx_staged(StreamCtx *c, const char *who, const char *what, void *d_stage_in, const void *host_in,
+                                        uint64_t n, State *state, Run run, CopyBack copy_back)
+{
+    return stream_ctx_staged_bytes(c, who, what, d_stage_in, host_in, (size_t)n * (c->in_i16 ? 4 : 8), state, run, copy_back);
 }
 
 } // namespace if_fir

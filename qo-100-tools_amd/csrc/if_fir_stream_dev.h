@@ -1,6 +1,6 @@
 // if_fir_stream_dev.h — what the kernel units of the streaming families (interpolator, channel combiner, rational resampler,
-// power spectrum) share: the device counterpart of if_fir_stream_ctx.h, under the same rule -- nothing here branches on which
-// family includes it.  The sample load of a call, the compensated addition, the single-LDS-reads attribute and the launchers'
+// power spectrum, real-input down-converter) share: the device counterpart of if_fir_stream_ctx.h, under the same rule --
+// nothing here branches on which family includes it.  The sample load of a call, the compensated addition, the single-LDS-reads attribute and the launchers'
 // grid sizes.  (ip_load, the interpolator's and the combiner's sample load, is in if_fir_interp_dev.h: DESIGN.md §3.11, Device side.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,6 +50,27 @@ __device__ __forceinline__ stream_v2f stream_load(const void *__restrict__ in, c
             v.x = s.x;
             v.y = s.y;
         }
+    }
+    return v;
+}
+
+// the same for a stream of REAL samples (one float32, or one int16 = value * 2^15, per sample; the history is float32)
+template <bool I16>
+__device__ __forceinline__ float stream_load_real(const void *__restrict__ in, const float *__restrict__ hist, int64_t hist_len, int64_t N,
+                                                  int64_t j)
+{
+    float v = 0.f;
+    if (j < 0)
+    {
+        if (j + hist_len >= 0)
+            v = hist[j + hist_len];
+    }
+    else if (j < N)
+    {
+        if constexpr (I16)
+            v = (float)static_cast<const short *>(in)[j] * (1.0f / 32768.0f);
+        else
+            v = static_cast<const float *>(in)[j];
     }
     return v;
 }

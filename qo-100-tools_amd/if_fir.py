@@ -42,6 +42,9 @@ EXPORTS = [
     "if_fir_combiner_get_backend", "if_fir_combiner_set_input_format", "if_fir_combiner_set_centres", "if_fir_combiner_get_centres",
     "if_fir_combiner_set_stream", "if_fir_combiner_synchronize", "if_fir_combiner_last_error", "if_fir_combiner_out_count",
     "if_fir_combiner_process", "if_fir_combiner_process_device",
+    "if_fir_ddc_init", "if_fir_ddc_init_complex", "if_fir_ddc_destroy", "if_fir_ddc_reset", "if_fir_ddc_set_input_format",
+    "if_fir_ddc_set_nco", "if_fir_ddc_get_nco", "if_fir_ddc_set_stream", "if_fir_ddc_synchronize", "if_fir_ddc_last_error",
+    "if_fir_ddc_out_count", "if_fir_ddc_process", "if_fir_ddc_process_device",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
@@ -49,7 +52,8 @@ DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_ta
                "if_fir_mc_debug_plan", "if_fir_debug_queue_faults",
                "if_fir_debug_interp_config", "if_fir_debug_interp_seek", "if_fir_debug_interp_tables", "if_fir_debug_interp_plan",
                "if_fir_debug_resamp_config", "if_fir_debug_psd_plan",
-               "if_fir_debug_combiner_config", "if_fir_debug_combiner_seek", "if_fir_debug_combiner_tables"]
+               "if_fir_debug_combiner_config", "if_fir_debug_combiner_seek", "if_fir_debug_combiner_tables",
+               "if_fir_debug_ddc_config"]
 MC_ID_BYTES = 128
 
 
@@ -169,13 +173,14 @@ def _load(path, dev):
     L.if_fir_mc_get_chunk_samples.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.if_fir_mc_get_chunk_samples.restype = u8
     # the streaming contexts (_StreamCtx): what the families declare alike, then what each has of its own
-    for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_"):
+    for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_", "if_fir_ddc_"):
         for name, args, res in (("destroy", [vp], None), ("reset", [vp], u8), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
                                 ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p)):
             getattr(L, prefix + name).argtypes = args
             getattr(L, prefix + name).restype = res
     for prefix, init_args in (("if_fir_interp_", [ctypes.POINTER(vp), f32p, u32, u32, u64, i32]),
-                              ("if_fir_resamp_", [ctypes.POINTER(vp), f32p, u32, u32, u32, u64, i32])):
+                              ("if_fir_resamp_", [ctypes.POINTER(vp), f32p, u32, u32, u32, u64, i32]),
+                              ("if_fir_ddc_", [ctypes.POINTER(vp), f32p, u32, u32, u64, i32])):
         for name, args, res in (("init", init_args, u8), ("init_complex", init_args, u8), ("out_count", [vp, u64], u64),
                                 ("process", [vp, vp, f32p, u64, ctypes.POINTER(u64)], u8),
                                 ("process_device", [vp, vp, vp, u64, ctypes.POINTER(u64)], u8)):
@@ -189,6 +194,10 @@ def _load(path, dev):
     L.if_fir_interp_set_nco.restype = u8
     L.if_fir_interp_get_nco.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     L.if_fir_interp_get_nco.restype = u8
+    L.if_fir_ddc_set_nco.argtypes = [vp, ctypes.c_double]
+    L.if_fir_ddc_set_nco.restype = u8
+    L.if_fir_ddc_get_nco.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+    L.if_fir_ddc_get_nco.restype = u8
     f64p = ctypes.POINTER(ctypes.c_double)
     for name in ("init", "init_complex"):
         getattr(L, "if_fir_combiner_" + name).argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u32, f64p, u64, i32]
@@ -227,6 +236,8 @@ def _load(path, dev):
         L.if_fir_debug_psd_plan.restype = u8
         L.if_fir_debug_resamp_config.argtypes = [vp, u32, ctypes.POINTER(u32)]
         L.if_fir_debug_resamp_config.restype = u8
+        L.if_fir_debug_ddc_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
+        L.if_fir_debug_ddc_config.restype = u8
         L.if_fir_debug_interp_config.argtypes = [vp, u32, u32]
         L.if_fir_debug_interp_config.restype = u8
         L.if_fir_debug_interp_seek.argtypes = [vp, u64]
@@ -483,7 +494,7 @@ class IfFir:
 
 
 class _StreamCtx:
-    """What IfFirInterp, IfFirResamp, IfFirPsd and IfFirCombiner share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
+    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner and IfFirDdc share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
     calls the three families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
     __init__, self._L, self._ctx and self._i16."""
     _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
@@ -763,6 +774,70 @@ class IfFirResamp(_StreamCtx):
             raise IfFirError("if_fir_debug_resamp_config is in the development library only: construct with dev=True")
         tile = ctypes.c_uint32(0)
         self._check(self._L.if_fir_debug_resamp_config(self._ctx, int(grid_limit), ctypes.byref(tile)))
+        self._grid_limit = int(grid_limit)
+        return int(tile.value)
+
+    def tile_outputs(self):
+        """outputs one workgroup computes per tile (development library); the grid limit stays as it is"""
+        return self.debug_config(self._grid_limit)
+
+
+class IfFirDdc(_StreamCtx):
+    """One if_fir_ddc_t: REAL IF samples to decimated complex baseband in one pass -- NCO down-mix, filter, keep every
+    decimation-th (docs/SPEC.md §10).  Methods mirror the C entry points; how many outputs a call emits depends on the stream
+    position (out_count)."""
+    _PREFIX = "if_fir_ddc_"
+    NO_POSITION = (1 << 64) - 1
+
+    def __init__(self, taps, decimation, max_samples=1 << 20, device=0, complex_taps=False, dev=False):
+        self._L = dev_lib() if dev else lib()
+        taps, count, complex_taps = _taps_arg(taps, complex_taps)
+        self._ctx = ctypes.c_void_p()
+        self.taps = taps
+        self.decimation = int(decimation)
+        self._i16 = False
+        self._dev, self._grid_limit = bool(dev), 0
+        init = self._L.if_fir_ddc_init_complex if complex_taps else self._L.if_fir_ddc_init
+        if not init(ctypes.byref(self._ctx), _f32p(taps), count, self.decimation, int(max_samples), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._c("last_error")(None).decode())
+
+    def set_nco(self, freq):
+        """if_fir_ddc_set_nco(): mix the input down by exp(-j 2 pi f a), a = absolute sample index; 0 = off."""
+        self._check(self._L.if_fir_ddc_set_nco(self._ctx, float(freq)))
+
+    def get_nco(self):
+        f = ctypes.c_double(0.0)
+        self._check(self._L.if_fir_ddc_get_nco(self._ctx, ctypes.byref(f)))
+        return float(f.value)
+
+    def out_count(self, samples):
+        """if_fir_ddc_out_count(): outputs of a call with `samples` inputs at the current stream position."""
+        return int(self._L.if_fir_ddc_out_count(self._ctx, int(samples)))
+
+    def _host_input(self, r):
+        """(contiguous float32 -- or int16 after set_input_format(INPUT_I16) -- array of REAL samples, sample count)"""
+        r = np.ascontiguousarray(r, dtype=np.int16 if self._i16 else np.float32).reshape(-1)
+        return r, r.size
+
+    def process(self, r):
+        """if_fir_ddc_process(): host float32 (or int16 after set_input_format(INPUT_I16)) real samples in, interleaved
+        float32 I, Q out."""
+        return self._process(r)
+
+    def process_device(self, dev_in, dev_out, samples):
+        """if_fir_ddc_process_device(): raw device pointers (ints), asynchronous.  Returns the output sample count."""
+        return self._process_device(dev_in, dev_out, samples)
+
+    def debug_config(self, grid_limit=0, position=None):
+        """if_fir_debug_ddc_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
+        launcher's choice); position (optional) = the absolute index of the next call's first sample, with the history zeroed.
+        Returns the outputs of one tile of this context."""
+        if not self._dev:
+            raise IfFirError("if_fir_debug_ddc_config is in the development library only: construct with dev=True")
+        tile = ctypes.c_uint32(0)
+        self._check(self._L.if_fir_debug_ddc_config(self._ctx, int(grid_limit), ctypes.byref(tile),
+                                                    self.NO_POSITION if position is None else int(position)))
         self._grid_limit = int(grid_limit)
         return int(tile.value)
 
