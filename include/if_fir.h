@@ -56,6 +56,13 @@ enum
     IF_FIR_INPUT_I16 = 1  /* interleaved int16 I,Q (4 bytes per sample), value = int16 * 2^-15  */
 };
 
+/* output sample formats of the real-output up-converter (if_fir_duc_set_output_format) */
+enum
+{
+    IF_FIR_OUTPUT_F32 = 0, /* one float32 per real sample (4 bytes), the default                                         */
+    IF_FIR_OUTPUT_I16 = 1  /* one int16 per real sample (2 bytes): the float32 result * 2^15, to nearest even, saturated */
+};
+
 /* window ids for if_bpf_design */
 enum
 {
@@ -431,6 +438,47 @@ uint8_t if_fir_ddc_process(if_fir_ddc_t *pCtx, const void *pIn, float *pfIQOut, 
 /* device pointers aligned to one sample (input 4 bytes, 2 for int16; output 8 bytes), asynchronous on the context's stream;
  * pDevOut holds if_fir_ddc_out_count() samples */
 uint8_t if_fir_ddc_process_device(if_fir_ddc_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples,
+                                  uint64_t *pullOutSamples);
+
+/* ---- real-output up-converter (docs/SPEC.md §11; BUILD-DEFINED) --------------------------------------------------------------
+ * Complex baseband x[n] to a REAL IF stream at L times the rate in ONE pass, the stage in front of a DAC:
+ *     u[m] = x[m/L] if m mod L == 0 else 0;   v[m] = sum_k h[k] u[m-k];   y[m] = Re{ exp(+j 2 pi ((P m) mod 2^32) / 2^32) v[m] }
+ * m = absolute OUTPUT index since init/reset, P = round(f * 2^32) mod 2^32 (if_fir_duc_set_nco; P = 0: no mixing): by definition
+ * the interpolator with if_fir_interp_set_nco followed by the real part.  L in 1..64, T <= 4096, taps real or complex.  A call
+ * with N inputs emits exactly N*L outputs.  process(a||b) == process(a); process(b), bit for bit, wherever the stream is cut.
+ * Errors: 0 + if_fir_duc_last_error(); a failed call leaves the context usable and its stream position unchanged.
+ * Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_duc if_fir_duc_t;
+
+uint8_t if_fir_duc_init(if_fir_duc_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulInterpolation, uint64_t ullMaxSamples,
+                        int32_t lDevice);
+/* complex taps: ulTaps interleaved (re, im) pairs */
+uint8_t if_fir_duc_init_complex(if_fir_duc_t **ppCtx, const float *pfTapsIQ, uint32_t ulTaps, uint32_t ulInterpolation,
+                                uint64_t ullMaxSamples, int32_t lDevice);
+void if_fir_duc_destroy(if_fir_duc_t *pCtx);
+/* zero the history and the stream position (the NCO frequency and the formats stay) */
+uint8_t if_fir_duc_reset(if_fir_duc_t *pCtx);
+/* IF_FIR_INPUT_F32 (8 bytes per sample) or IF_FIR_INPUT_I16 (4 bytes, value = int16 * 2^-15); the history is float32, so a
+ * change keeps the stream */
+uint8_t if_fir_duc_set_input_format(if_fir_duc_t *pCtx, uint32_t ulFormat);
+/* IF_FIR_OUTPUT_F32 (4 bytes per sample, the default) or IF_FIR_OUTPUT_I16 (2 bytes: the same float32 result * 2^15, rounded
+ * to nearest even, saturated to -32768..32767); a change keeps the stream */
+uint8_t if_fir_duc_set_output_format(if_fir_duc_t *pCtx, uint32_t ulFormat);
+/* dFreq in cycles per OUTPUT sample, |dFreq| <= 0.5; holds from the next call as if set since the last reset (the phase is a
+ * function of the absolute index only).  Waits for the context's stream. */
+uint8_t if_fir_duc_set_nco(if_fir_duc_t *pCtx, double dFreq);
+/* the quantised frequency P / 2^32, P read as a signed word */
+uint8_t if_fir_duc_get_nco(const if_fir_duc_t *pCtx, double *pdFreq);
+uint8_t if_fir_duc_set_stream(if_fir_duc_t *pCtx, void *pStream);
+uint8_t if_fir_duc_synchronize(if_fir_duc_t *pCtx);
+const char *if_fir_duc_last_error(const if_fir_duc_t *pCtx);
+/* outputs of a call with ullSamples inputs: ullSamples * L (0 where the stream position would pass 2^64 outputs) */
+uint64_t if_fir_duc_out_count(const if_fir_duc_t *pCtx, uint64_t ullSamples);
+/* host pointers, synchronous; ullSamples <= ullMaxSamples of init; pOut holds if_fir_duc_out_count() float32 or int16 */
+uint8_t if_fir_duc_process(if_fir_duc_t *pCtx, const void *pIQIn, void *pOut, uint64_t ullSamples, uint64_t *pullOutSamples);
+/* device pointers aligned to one element (input 8 bytes, 4 for int16; output 4 bytes, 2 for int16), asynchronous on the
+ * context's stream; pDevOut holds if_fir_duc_out_count() elements */
+uint8_t if_fir_duc_process_device(if_fir_duc_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples,
                                   uint64_t *pullOutSamples);
 
 #ifdef __cplusplus

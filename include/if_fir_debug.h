@@ -108,6 +108,10 @@ uint8_t if_fir_debug_resamp_config(if_fir_resamp_t *pCtx, uint32_t ulGridLimit, 
 /* down-converter (if_fir_ddc_t): ulGridLimit and *pulTileOutputs as if_fir_debug_resamp_config; an ullPosition other than
  * UINT64_MAX sets the context's absolute sample index (the index of the next call's first sample) and zeroes its history */
 uint8_t if_fir_debug_ddc_config(if_fir_ddc_t *pCtx, uint32_t ulGridLimit, uint32_t *pulTileOutputs, uint64_t ullPosition);
+/* up-converter (if_fir_duc_t): ulGridLimit as if_fir_debug_resamp_config; *pulTileInputs (may be NULL) receives the INPUT samples
+ * of one tile of this context (a tile emits L times as many outputs); an ullPosition other than UINT64_MAX sets the count of
+ * input samples consumed since reset (the index of the next call's first input) and zeroes the history */
+uint8_t if_fir_debug_duc_config(if_fir_duc_t *pCtx, uint32_t ulGridLimit, uint32_t *pulTileInputs, uint64_t ullPosition);
 /* power-spectrum estimator (if_fir_psd_t): the plan of the next call of ullSamples samples at the current stream position:
  * pullPlan[0..3] = segments summed, chunks summed, frames emitted, samples carried after the call (nothing runs) */
 uint8_t if_fir_debug_psd_plan(const if_fir_psd_t *pCtx, uint64_t ullSamples, uint64_t *pullPlan);

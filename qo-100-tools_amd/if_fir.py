@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libif_fir.so")
 DEV_LIB_PATH = os.path.join(_HERE, "libif_fir_dev.so")
 
 INPUT_F32, INPUT_I16 = 0, 1
+OUTPUT_F32, OUTPUT_I16 = 0, 1
 BACKEND_AUTO, BACKEND_HIP_DIRECT, BACKEND_HIP_TAPSPLIT, BACKEND_HIP_GENERIC, BACKEND_HIP_FFT = range(5)
 WINDOW_RECT, WINDOW_HAMMING, WINDOW_HANN, WINDOW_BLACKMAN = range(4)
 
@@ -45,6 +46,9 @@ EXPORTS = [
     "if_fir_ddc_init", "if_fir_ddc_init_complex", "if_fir_ddc_destroy", "if_fir_ddc_reset", "if_fir_ddc_set_input_format",
     "if_fir_ddc_set_nco", "if_fir_ddc_get_nco", "if_fir_ddc_set_stream", "if_fir_ddc_synchronize", "if_fir_ddc_last_error",
     "if_fir_ddc_out_count", "if_fir_ddc_process", "if_fir_ddc_process_device",
+    "if_fir_duc_init", "if_fir_duc_init_complex", "if_fir_duc_destroy", "if_fir_duc_reset", "if_fir_duc_set_input_format",
+    "if_fir_duc_set_output_format", "if_fir_duc_set_nco", "if_fir_duc_get_nco", "if_fir_duc_set_stream", "if_fir_duc_synchronize",
+    "if_fir_duc_last_error", "if_fir_duc_out_count", "if_fir_duc_process", "if_fir_duc_process_device",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
@@ -53,7 +57,7 @@ DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_ta
                "if_fir_debug_interp_config", "if_fir_debug_interp_seek", "if_fir_debug_interp_tables", "if_fir_debug_interp_plan",
                "if_fir_debug_resamp_config", "if_fir_debug_psd_plan",
                "if_fir_debug_combiner_config", "if_fir_debug_combiner_seek", "if_fir_debug_combiner_tables",
-               "if_fir_debug_ddc_config"]
+               "if_fir_debug_ddc_config", "if_fir_debug_duc_config"]
 MC_ID_BYTES = 128
 
 
@@ -173,7 +177,7 @@ def _load(path, dev):
     L.if_fir_mc_get_chunk_samples.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.if_fir_mc_get_chunk_samples.restype = u8
     # the streaming contexts (_StreamCtx): what the families declare alike, then what each has of its own
-    for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_", "if_fir_ddc_"):
+    for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_", "if_fir_ddc_", "if_fir_duc_"):
         for name, args, res in (("destroy", [vp], None), ("reset", [vp], u8), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
                                 ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p)):
             getattr(L, prefix + name).argtypes = args
@@ -198,6 +202,13 @@ def _load(path, dev):
     L.if_fir_ddc_set_nco.restype = u8
     L.if_fir_ddc_get_nco.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     L.if_fir_ddc_get_nco.restype = u8
+    for name, args, res in (("init", [ctypes.POINTER(vp), f32p, u32, u32, u64, i32], u8),
+                            ("init_complex", [ctypes.POINTER(vp), f32p, u32, u32, u64, i32], u8), ("out_count", [vp, u64], u64),
+                            ("process", [vp, vp, vp, u64, ctypes.POINTER(u64)], u8),
+                            ("process_device", [vp, vp, vp, u64, ctypes.POINTER(u64)], u8), ("set_output_format", [vp, u32], u8),
+                            ("set_nco", [vp, ctypes.c_double], u8), ("get_nco", [vp, ctypes.POINTER(ctypes.c_double)], u8)):
+        getattr(L, "if_fir_duc_" + name).argtypes = args
+        getattr(L, "if_fir_duc_" + name).restype = res
     f64p = ctypes.POINTER(ctypes.c_double)
     for name in ("init", "init_complex"):
         getattr(L, "if_fir_combiner_" + name).argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u32, f64p, u64, i32]
@@ -238,6 +249,8 @@ def _load(path, dev):
         L.if_fir_debug_resamp_config.restype = u8
         L.if_fir_debug_ddc_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
         L.if_fir_debug_ddc_config.restype = u8
+        L.if_fir_debug_duc_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
+        L.if_fir_debug_duc_config.restype = u8
         L.if_fir_debug_interp_config.argtypes = [vp, u32, u32]
         L.if_fir_debug_interp_config.restype = u8
         L.if_fir_debug_interp_seek.argtypes = [vp, u64]
@@ -494,7 +507,7 @@ class IfFir:
 
 
 class _StreamCtx:
-    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner and IfFirDdc share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
+    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc and IfFirDuc share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
     calls the three families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
     __init__, self._L, self._ctx and self._i16."""
     _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
@@ -843,6 +856,77 @@ class IfFirDdc(_StreamCtx):
 
     def tile_outputs(self):
         """outputs one workgroup computes per tile (development library); the grid limit stays as it is"""
+        return self.debug_config(self._grid_limit)
+
+
+class IfFirDuc(_StreamCtx):
+    """One if_fir_duc_t: complex baseband to a REAL IF stream at `interpolation` times the rate in one pass -- upsample, filter,
+    NCO up-mix, real part, optionally int16 (docs/SPEC.md §11).  Methods mirror the C entry points; N input samples give
+    N * interpolation real outputs, float32 or (after set_output_format(OUTPUT_I16)) int16."""
+    _PREFIX = "if_fir_duc_"
+    NO_POSITION = (1 << 64) - 1
+
+    def __init__(self, taps, interpolation, max_samples=1 << 20, device=0, complex_taps=False, dev=False):
+        self._L = dev_lib() if dev else lib()
+        taps, count, complex_taps = _taps_arg(taps, complex_taps)
+        self._ctx = ctypes.c_void_p()
+        self.taps = taps
+        self.interpolation = int(interpolation)
+        self._i16 = self._o16 = False
+        self._dev, self._grid_limit = bool(dev), 0
+        init = self._L.if_fir_duc_init_complex if complex_taps else self._L.if_fir_duc_init
+        if not init(ctypes.byref(self._ctx), _f32p(taps), count, self.interpolation, int(max_samples), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._c("last_error")(None).decode())
+
+    def set_output_format(self, fmt):
+        """if_fir_duc_set_output_format(): OUTPUT_F32 or OUTPUT_I16 (the float32 result times 2^15, to nearest even, saturated)."""
+        self._check(self._L.if_fir_duc_set_output_format(self._ctx, int(fmt)))
+        self._o16 = (int(fmt) == OUTPUT_I16)
+
+    def set_nco(self, freq):
+        """if_fir_duc_set_nco(): mix the output up by exp(+j 2 pi f m), m = absolute output index, before the real part; 0 = off."""
+        self._check(self._L.if_fir_duc_set_nco(self._ctx, float(freq)))
+
+    def get_nco(self):
+        f = ctypes.c_double(0.0)
+        self._check(self._L.if_fir_duc_get_nco(self._ctx, ctypes.byref(f)))
+        return float(f.value)
+
+    def out_count(self, samples):
+        """if_fir_duc_out_count(): samples * interpolation."""
+        return int(self._L.if_fir_duc_out_count(self._ctx, int(samples)))
+
+    def process(self, iq):
+        """if_fir_duc_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in, real
+        float32 (or int16 after set_output_format(OUTPUT_I16)) out."""
+        iq, n = self._host_input(iq)
+        out = np.empty(self.out_count(n), dtype=np.int16 if self._o16 else np.float32)
+        m = ctypes.c_uint64(0)
+        dummy = np.zeros(2, dtype=np.float32)
+        self._check(self._L.if_fir_duc_process(self._ctx, ctypes.c_void_p(iq.ctypes.data if n else dummy.ctypes.data),
+                                               ctypes.c_void_p(out.ctypes.data if out.size else dummy.ctypes.data), n, ctypes.byref(m)))
+        assert m.value == out.size
+        return out
+
+    def process_device(self, dev_in, dev_out, samples):
+        """if_fir_duc_process_device(): raw device pointers (ints), asynchronous.  Returns the output sample count."""
+        return self._process_device(dev_in, dev_out, samples)
+
+    def debug_config(self, grid_limit=0, position=None):
+        """if_fir_debug_duc_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
+        launcher's choice); position (optional) = the count of input samples before the next call, with the history zeroed.
+        Returns the INPUT samples of one tile of this context."""
+        if not self._dev:
+            raise IfFirError("if_fir_debug_duc_config is in the development library only: construct with dev=True")
+        tile = ctypes.c_uint32(0)
+        self._check(self._L.if_fir_debug_duc_config(self._ctx, int(grid_limit), ctypes.byref(tile),
+                                                    self.NO_POSITION if position is None else int(position)))
+        self._grid_limit = int(grid_limit)
+        return int(tile.value)
+
+    def tile_inputs(self):
+        """input samples one workgroup takes per tile (development library); the grid limit stays as it is"""
         return self.debug_config(self._grid_limit)
 
 
