@@ -481,6 +481,51 @@ uint8_t if_fir_duc_process(if_fir_duc_t *pCtx, const void *pIQIn, void *pOut, ui
 uint8_t if_fir_duc_process_device(if_fir_duc_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples,
                                   uint64_t *pullOutSamples);
 
+/* ---- arbitrary-ratio resampler with a retunable step (docs/SPEC.md §12; BUILD-DEFINED) ---------------------------------------
+ * Changes a stream's rate by ANY ratio in the range below, and lets the ratio be nudged between calls without restarting the
+ * stream.  The prototype h[0..T-1] (real float32, T <= 8192) is designed at P = 2^ulPhaseBits times the input rate (4 <=
+ * ulPhaseBits <= 10) and is used as given: unity pass-band gain needs sum h = P.  K = ceil(T/P) taps per phase.  The step
+ * ullStep = R is input samples per output sample times 2^32, 2^26 <= R <= 2^34 (ratios 1/64 .. 4).  The context keeps c, the
+ * absolute index of the next input (64 bits), and tau, the time of the next output in units of 2^-32 input samples (96 bits);
+ * both are 0 after init and reset.  One output:
+ *     q = floor(tau / 2^32), f = tau mod 2^32, p = the top ulPhaseBits bits of f, mu = (the other bits of f) / 2^(32-ulPhaseBits)
+ *     y = sum_{j<K} [(1-mu) h[p + j*P] + mu h[p+1 + j*P]] x[q-j]      (h[k] = 0 for k >= T, x[i] = 0 for i < 0);   tau += R
+ * A call that brings the inputs [c, c+N) emits, in order, every output with floor(tau / 2^32) < c+N:
+ * max(0, ceil(((c+N)*2^32 - tau) / R)) of them, possibly none; then c += N.  All of this is integer arithmetic, so
+ * process(a||b) == process(a); process(b), bit for bit, wherever the stream is cut.  Float32 or int16 input; float32 I/Q output.
+ * No NCO, real taps only.  Errors: 0 + if_fir_arb_last_error(); a failed call leaves the context usable and c, tau unchanged.
+ * Calls on a stream that is being captured into a hipGraph are refused. */
+#define IF_FIR_ARB_MAX_TAPS 8192u
+#define IF_FIR_ARB_MIN_PHASE_BITS 4u
+#define IF_FIR_ARB_MAX_PHASE_BITS 10u
+typedef struct if_fir_arb if_fir_arb_t;
+
+/* ullMaxSamples: 1..2^30, the most inputs of one if_fir_arb_process() call */
+uint8_t if_fir_arb_init(if_fir_arb_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulPhaseBits, uint64_t ullStep,
+                        uint64_t ullMaxSamples, int32_t lDevice);
+void if_fir_arb_destroy(if_fir_arb_t *pCtx);
+/* zero the history, c and tau; the step stays */
+uint8_t if_fir_arb_reset(if_fir_arb_t *pCtx);
+/* retune between calls: c, tau and the history stay, so the next output is where it was and the one after it ullStep later.
+ * Setting the current value changes no bit. */
+uint8_t if_fir_arb_set_step(if_fir_arb_t *pCtx, uint64_t ullStep);
+/* IF_FIR_INPUT_F32 or IF_FIR_INPUT_I16 (value = int16 * 2^-15); the history is float32, so a change keeps the stream */
+uint8_t if_fir_arb_set_input_format(if_fir_arb_t *pCtx, uint32_t ulFormat);
+uint8_t if_fir_arb_set_stream(if_fir_arb_t *pCtx, void *pStream);
+uint8_t if_fir_arb_synchronize(if_fir_arb_t *pCtx);
+const char *if_fir_arb_last_error(const if_fir_arb_t *pCtx);
+/* outputs of a call with ullSamples inputs at the current position and step */
+uint64_t if_fir_arb_out_count(const if_fir_arb_t *pCtx, uint64_t ullSamples);
+/* host pointers, synchronous; ullSamples <= ullMaxSamples of init; pfIQOut holds if_fir_arb_out_count() samples */
+uint8_t if_fir_arb_process(if_fir_arb_t *pCtx, const void *pIQIn, float *pfIQOut, uint64_t ullSamples, uint64_t *pullOutSamples);
+/* device pointers aligned to one sample (input 8 bytes, 4 for int16; output 8 bytes), asynchronous on the context's stream;
+ * ullSamples <= 2^36; pDevOut holds if_fir_arb_out_count() samples */
+uint8_t if_fir_arb_process_device(if_fir_arb_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples,
+                                  uint64_t *pullOutSamples);
+/* the step for a pair of rates: rint(dRateIn / dRateOut * 2^32), or 0 when that is outside 2^26 .. 2^34 or a rate is not a
+ * positive finite number.  Touches no context and no GPU. */
+uint64_t if_fir_arb_step_from_rates(double dRateIn, double dRateOut);
+
 #ifdef __cplusplus
 }
 #endif

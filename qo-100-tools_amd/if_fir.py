@@ -49,6 +49,9 @@ EXPORTS = [
     "if_fir_duc_init", "if_fir_duc_init_complex", "if_fir_duc_destroy", "if_fir_duc_reset", "if_fir_duc_set_input_format",
     "if_fir_duc_set_output_format", "if_fir_duc_set_nco", "if_fir_duc_get_nco", "if_fir_duc_set_stream", "if_fir_duc_synchronize",
     "if_fir_duc_last_error", "if_fir_duc_out_count", "if_fir_duc_process", "if_fir_duc_process_device",
+    "if_fir_arb_init", "if_fir_arb_destroy", "if_fir_arb_reset", "if_fir_arb_set_step", "if_fir_arb_set_input_format",
+    "if_fir_arb_set_stream", "if_fir_arb_synchronize", "if_fir_arb_last_error", "if_fir_arb_out_count", "if_fir_arb_process",
+    "if_fir_arb_process_device", "if_fir_arb_step_from_rates",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
@@ -57,7 +60,7 @@ DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_ta
                "if_fir_debug_interp_config", "if_fir_debug_interp_seek", "if_fir_debug_interp_tables", "if_fir_debug_interp_plan",
                "if_fir_debug_resamp_config", "if_fir_debug_psd_plan",
                "if_fir_debug_combiner_config", "if_fir_debug_combiner_seek", "if_fir_debug_combiner_tables",
-               "if_fir_debug_ddc_config", "if_fir_debug_duc_config"]
+               "if_fir_debug_ddc_config", "if_fir_debug_duc_config", "if_fir_debug_arb_config"]
 MC_ID_BYTES = 128
 
 
@@ -177,7 +180,7 @@ def _load(path, dev):
     L.if_fir_mc_get_chunk_samples.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.if_fir_mc_get_chunk_samples.restype = u8
     # the streaming contexts (_StreamCtx): what the families declare alike, then what each has of its own
-    for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_", "if_fir_ddc_", "if_fir_duc_"):
+    for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_", "if_fir_ddc_", "if_fir_duc_", "if_fir_arb_"):
         for name, args, res in (("destroy", [vp], None), ("reset", [vp], u8), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
                                 ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p)):
             getattr(L, prefix + name).argtypes = args
@@ -209,6 +212,12 @@ def _load(path, dev):
                             ("set_nco", [vp, ctypes.c_double], u8), ("get_nco", [vp, ctypes.POINTER(ctypes.c_double)], u8)):
         getattr(L, "if_fir_duc_" + name).argtypes = args
         getattr(L, "if_fir_duc_" + name).restype = res
+    for name, args, res in (("init", [ctypes.POINTER(vp), f32p, u32, u32, u64, u64, i32], u8), ("set_step", [vp, u64], u8),
+                            ("out_count", [vp, u64], u64), ("process", [vp, vp, f32p, u64, ctypes.POINTER(u64)], u8),
+                            ("process_device", [vp, vp, vp, u64, ctypes.POINTER(u64)], u8),
+                            ("step_from_rates", [ctypes.c_double, ctypes.c_double], u64)):
+        getattr(L, "if_fir_arb_" + name).argtypes = args
+        getattr(L, "if_fir_arb_" + name).restype = res
     f64p = ctypes.POINTER(ctypes.c_double)
     for name in ("init", "init_complex"):
         getattr(L, "if_fir_combiner_" + name).argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u32, f64p, u64, i32]
@@ -251,6 +260,8 @@ def _load(path, dev):
         L.if_fir_debug_ddc_config.restype = u8
         L.if_fir_debug_duc_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
         L.if_fir_debug_duc_config.restype = u8
+        L.if_fir_debug_arb_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64, u64]
+        L.if_fir_debug_arb_config.restype = u8
         L.if_fir_debug_interp_config.argtypes = [vp, u32, u32]
         L.if_fir_debug_interp_config.restype = u8
         L.if_fir_debug_interp_seek.argtypes = [vp, u64]
@@ -507,7 +518,7 @@ class IfFir:
 
 
 class _StreamCtx:
-    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc and IfFirDuc share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
+    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc and IfFirArb share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
     calls the three families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
     __init__, self._L, self._ctx and self._i16."""
     _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
@@ -792,6 +803,75 @@ class IfFirResamp(_StreamCtx):
 
     def tile_outputs(self):
         """outputs one workgroup computes per tile (development library); the grid limit stays as it is"""
+        return self.debug_config(self._grid_limit)
+
+
+def step_from_rates(rate_in, rate_out):
+    """if_fir_arb_step_from_rates(): the IfFirArb step for a pair of rates, rint(rate_in / rate_out * 2^32); 0 when that is
+    outside 2^26 .. 2^34.  No context, no GPU."""
+    return int(lib().if_fir_arb_step_from_rates(float(rate_in), float(rate_out)))
+
+
+class IfFirArb(_StreamCtx):
+    """One if_fir_arb_t: change the rate by any ratio 1/64 .. 4 with a step that can be retuned between calls (docs/SPEC.md
+    §12).  `taps` is the real prototype designed at 2^phase_bits times the input rate; `step` is input samples per output
+    sample times 2^32.  Methods mirror the C entry points; how many outputs a call emits depends on the position (out_count)."""
+    _PREFIX = "if_fir_arb_"
+
+    def __init__(self, taps, phase_bits, step, max_samples=1 << 20, device=0, dev=False):
+        self._L = dev_lib() if dev else lib()
+        taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        self._ctx = ctypes.c_void_p()
+        self.taps = taps
+        self.phase_bits, self._step = int(phase_bits), int(step)
+        self._i16 = False
+        self._dev, self._grid_limit = bool(dev), 0
+        if not (0 <= self.phase_bits < 1 << 32 and 0 <= self._step < 1 << 64):
+            raise IfFirError("if_fir_arb_init: phase bits and step must be unsigned (got %d, %d)" % (self.phase_bits, self._step))
+        if not self._L.if_fir_arb_init(ctypes.byref(self._ctx), _f32p(taps), taps.size, self.phase_bits, self._step,
+                                       int(max_samples), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._c("last_error")(None).decode())
+
+    @property
+    def step(self):
+        """the step in force: input samples per output sample times 2^32"""
+        return self._step
+
+    def set_step(self, step):
+        """if_fir_arb_set_step(): retune between calls; the position, the time of the next output and the history stay."""
+        if not 0 <= int(step) < 1 << 64:
+            raise IfFirError("if_fir_arb_set_step: step must be 2^26..2^34 (got %d)" % int(step))
+        self._check(self._L.if_fir_arb_set_step(self._ctx, int(step)))
+        self._step = int(step)
+
+    def out_count(self, samples):
+        """if_fir_arb_out_count(): outputs of a call with `samples` inputs at the current position and step."""
+        return int(self._L.if_fir_arb_out_count(self._ctx, int(samples)))
+
+    def process(self, iq):
+        """if_fir_arb_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in,
+        interleaved float32 out."""
+        return self._process(iq)
+
+    def process_device(self, dev_in, dev_out, samples):
+        """if_fir_arb_process_device(): raw device pointers (ints), asynchronous.  Returns the output sample count."""
+        return self._process_device(dev_in, dev_out, samples)
+
+    def debug_config(self, grid_limit=0, position=None, time_offset=0):
+        """if_fir_debug_arb_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
+        launcher's choice); with `position`, on a freshly reset context, the next input has that absolute index and the next
+        output comes time_offset / 2^32 samples after it.  Returns the outputs of one tile of this context."""
+        if not self._dev:
+            raise IfFirError("if_fir_debug_arb_config is in the development library only: construct with dev=True")
+        tile = ctypes.c_uint32(0)
+        pos = (1 << 64) - 1 if position is None else int(position)
+        self._check(self._L.if_fir_debug_arb_config(self._ctx, int(grid_limit), ctypes.byref(tile), pos, int(time_offset)))
+        self._grid_limit = int(grid_limit)
+        return int(tile.value)
+
+    def tile_outputs(self):
+        """outputs one workgroup computes per tile (development library); the grid limit and the position stay as they are"""
         return self.debug_config(self._grid_limit)
 
 
