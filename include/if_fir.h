@@ -526,6 +526,47 @@ uint8_t if_fir_arb_process_device(if_fir_arb_t *pCtx, const void *pDevIn, void *
  * positive finite number.  Touches no context and no GPU. */
 uint64_t if_fir_arb_step_from_rates(double dRateIn, double dRateOut);
 
+/* ---- polyphase filter bank (docs/SPEC.md §13; BUILD-DEFINED) ------------------------------------------------------------------
+ * ALL M channels of a uniform grid out of one complex IQ stream in ONE pass (the analysis bank also known as PFB or weighted
+ * overlap-add), M = 64 .. 4096.  Channel k is the decimator of SPEC §3.2 with phase word k * 2^32 / M, the real prototype
+ * h[0..T-1] (T <= 16 M) and decimation D = ulHop (1 <= D <= M, any integer):
+ *     y_k[m] = sum_{t<T} h[t] x[a-t] exp(-j 2 pi k (a-t) / M),   a = m*D = absolute index since init/reset,   x[i<0] = 0
+ * Output is complex64 (float32 I, Q), frame-major: out[m*ulBins + j] = channel (lFirstBin + j) mod M of frame m.  A call whose
+ * first sample has absolute index c and which brings N samples emits the frames with m*D in [c, c+N) (possibly none).
+ * process(a||b) == process(a); process(b), bit for bit, wherever the stream is cut.  Float32 or int16 input.
+ * The filter bank of if_fir_channelizer_process_device stays the route for up to 16 channels.
+ * Errors: 0 + if_fir_pfb_last_error(); a failed call leaves the context usable and its stream position unchanged.
+ * Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_pfb if_fir_pfb_t;
+
+typedef struct
+{
+    uint32_t ulChannels; /* M: 64, 128, 256, 512, 1024, 2048 or 4096 */
+    uint32_t ulHop;      /* D: input samples per frame, 1..M */
+    int32_t lFirstBin;   /* first output channel, -M/2 <= lFirstBin < M (negative: counted down from M) */
+    uint32_t ulBins;     /* output channels per frame, 1..M; the span wraps at M */
+} if_fir_pfb_config_t;
+
+/* pfTaps: ulTaps real float32 taps, 1 <= ulTaps <= 16 M, used as given.  ullMaxSamples: 1..2^40, the most samples of one call */
+uint8_t if_fir_pfb_init(if_fir_pfb_t **ppCtx, const if_fir_pfb_config_t *pCfg, const float *pfTaps, uint32_t ulTaps,
+                        uint64_t ullMaxSamples, int32_t lDevice);
+void if_fir_pfb_destroy(if_fir_pfb_t *pCtx);
+/* zero the history and the stream position */
+uint8_t if_fir_pfb_reset(if_fir_pfb_t *pCtx);
+/* IF_FIR_INPUT_F32 or IF_FIR_INPUT_I16 (value = int16 * 2^-15); the history is float32, so a change keeps the stream */
+uint8_t if_fir_pfb_set_input_format(if_fir_pfb_t *pCtx, uint32_t ulFormat);
+uint8_t if_fir_pfb_set_stream(if_fir_pfb_t *pCtx, void *pStream);
+uint8_t if_fir_pfb_synchronize(if_fir_pfb_t *pCtx);
+const char *if_fir_pfb_last_error(const if_fir_pfb_t *pCtx);
+/* frames a call with ullSamples samples would emit at the current stream position */
+uint64_t if_fir_pfb_frame_count(const if_fir_pfb_t *pCtx, uint64_t ullSamples);
+/* host pointers, synchronous; ullSamples <= ullMaxSamples of init; pfIQOut holds if_fir_pfb_frame_count() x ulBins samples;
+ * *pullFrames (may be NULL) receives the frames emitted */
+uint8_t if_fir_pfb_process(if_fir_pfb_t *pCtx, const void *pIQIn, float *pfIQOut, uint64_t ullSamples, uint64_t *pullFrames);
+/* device pointers aligned to one sample (input 8 bytes, 4 for int16; output 8 bytes), asynchronous on the context's stream;
+ * pDevOut holds if_fir_pfb_frame_count() x ulBins samples */
+uint8_t if_fir_pfb_process_device(if_fir_pfb_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples, uint64_t *pullFrames);
+
 #ifdef __cplusplus
 }
 #endif

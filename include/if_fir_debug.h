@@ -119,6 +119,10 @@ uint8_t if_fir_debug_psd_plan(const if_fir_psd_t *pCtx, uint64_t ullSamples, uin
  * than UINT64_MAX, on a freshly reset context, sets c = ullPosition and tau = c * 2^32 + ullTimeOffset (ullTimeOffset < 2^34) */
 uint8_t if_fir_debug_arb_config(if_fir_arb_t *pCtx, uint32_t ulGridLimit, uint32_t *pulTileOutputs, uint64_t ullPosition,
                                 uint64_t ullTimeOffset);
+/* polyphase filter bank (if_fir_pfb_t): ulGridLimit as if_fir_debug_resamp_config; *pulGroupFrames (may be NULL) receives the
+ * consecutive frames one workgroup owns; an ullPosition other than UINT64_MAX sets the context's absolute sample index (the
+ * index of the next call's first sample) and zeroes its history */
+uint8_t if_fir_debug_pfb_config(if_fir_pfb_t *pCtx, uint32_t ulGridLimit, uint32_t *pulGroupFrames, uint64_t ullPosition);
 
 #ifdef __cplusplus
 }

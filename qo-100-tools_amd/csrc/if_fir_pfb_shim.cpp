@@ -1,0 +1,327 @@
+// if_fir_pfb_shim.cpp — the C ABI of the polyphase filter bank (include/if_fir.h, if_fir_pfb_*; docs/SPEC.md §13).  Its own
+// opaque context beside the other streaming families.  Same conventions: 1/0 status, a message per context, no CPU fallback.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "if_fir.h"
+#ifdef IF_FIR_DEVELOPMENT
+#include "if_fir_debug.h"
+#endif
+#include "if_fir_pfb.h"
+#include "if_fir_stream_ctx.h"
+
+#define IF_FIR_API extern "C" __attribute__((visibility("default")))
+
+// the streaming state: what a call advances (and a failed if_fir_pfb_process puts back)
+struct pfb_state
+{
+    int hist_cur;
+    uint64_t position;        // input samples since init/reset
+};
+
+struct if_fir_pfb : if_fir::StreamCtx
+{
+    int M, T, K, D, bins;
+    float *d_taps;            // the table of pfb_build_taps
+    float2 *d_twiddle;
+    uint16_t *d_bin_pos;
+    float2 *d_hist[2];        // the last T - 1 input samples, float32, ping-pong
+    int hist_len;
+    pfb_state st;
+    void *d_stage_in;         // if_fir_pfb_process: staging, allocated by its first call (device-pointer users never pay for it)
+    float2 *d_stage_out;
+    int grid_limit;           // development hook
+};
+
+using if_fir::set_err;
+static thread_local char g_pfb_init_err[256] = "";
+
+static void free_ctx(if_fir_pfb *c)
+{
+    if (!c)
+        return;
+    if_fir::stream_ctx_close(c, {c->d_taps, c->d_twiddle, c->d_bin_pos, c->d_hist[0], c->d_hist[1], c->d_stage_in, c->d_stage_out});
+    delete c;
+}
+
+IF_FIR_API uint8_t if_fir_pfb_init(if_fir_pfb_t **ppCtx, const if_fir_pfb_config_t *pCfg, const float *pfTaps, uint32_t ulTaps,
+                                   uint64_t ullMaxSamples, int32_t lDevice)
+{
+    if (!ppCtx)
+    {
+        set_err(g_pfb_init_err, "if_fir_pfb_init: ppCtx is NULL");
+        return 0;
+    }
+    *ppCtx = nullptr;
+    if (!pCfg)
+    {
+        set_err(g_pfb_init_err, "if_fir_pfb_init: pCfg is NULL");
+        return 0;
+    }
+    const uint32_t M = pCfg->ulChannels;
+    if (!if_fir::pfb_size_ok(M))
+    {
+        set_err(g_pfb_init_err, "if_fir_pfb_init: channels must be 64, 128, 256, 512, 1024, 2048 or 4096 (got %u)", M);
+        return 0;
+    }
+    if (!pfTaps || ulTaps < 1 || ulTaps > (uint32_t)if_fir::PFB_MAX_ROWS * M)
+    {
+        set_err(g_pfb_init_err, "if_fir_pfb_init: taps must be 1..%u = 16 x channels (got %u)%s", (uint32_t)if_fir::PFB_MAX_ROWS * M, ulTaps,
+                pfTaps ? "" : ", pfTaps is NULL");
+        return 0;
+    }
+    if (pCfg->ulHop < 1 || pCfg->ulHop > M)
+    {
+        set_err(g_pfb_init_err, "if_fir_pfb_init: hop must be 1..%u (got %u)", M, pCfg->ulHop);
+        return 0;
+    }
+    const int64_t half = (int64_t)M / 2, first = pCfg->lFirstBin;
+    if (pCfg->ulBins < 1 || pCfg->ulBins > M || first < -half || first >= (int64_t)M)
+    {
+        set_err(g_pfb_init_err, "if_fir_pfb_init: the span needs -%lld <= lFirstBin < %u and 1 <= ulBins <= %u (got %d, %u)", (long long)half,
+                M, M, pCfg->lFirstBin, pCfg->ulBins);
+        return 0;
+    }
+    if (ullMaxSamples == 0 || ullMaxSamples > if_fir::PFB_MAX_CALL)
+    {
+        set_err(g_pfb_init_err, "if_fir_pfb_init: ullMaxSamples must be 1..2^40 (got %llu)", (unsigned long long)ullMaxSamples);
+        return 0;
+    }
+    const uint32_t T = ulTaps, K = if_fir::pfb_rows(T, M), bins = pCfg->ulBins;
+    std::vector<float> table((size_t)K * M);
+    if_fir::pfb_build_taps(pfTaps, T, M, table.data());
+    std::vector<float> twiddle(2 * (size_t)M);
+    for (uint32_t t = 0; t < M; t++)
+    {
+        const double ang = -2.0 * M_PI * (double)t / (double)M;
+        twiddle[2 * t] = (float)cos(ang);
+        twiddle[2 * t + 1] = (float)sin(ang);
+    }
+    std::vector<uint16_t> where(bins);
+    for (uint32_t j = 0; j < bins; j++)
+        where[j] = (uint16_t)if_fir::pfb_bin_place(pCfg->lFirstBin, j, M);
+
+    if (!if_fir::stream_ctx_device_ok(g_pfb_init_err, "if_fir_pfb_init", lDevice))
+        return 0;
+    if_fir_pfb *c = new (std::nothrow) if_fir_pfb();
+    if (!c)
+    {
+        set_err(g_pfb_init_err, "if_fir_pfb_init: out of host memory");
+        return 0;
+    }
+    c->M = (int)M;
+    c->T = (int)T;
+    c->K = (int)K;
+    c->D = (int)pCfg->ulHop;
+    c->bins = (int)bins;
+    c->hist_len = (int)T - 1;
+    const size_t hist_bytes = (size_t)(c->hist_len > 0 ? c->hist_len : 1) * sizeof(float2);
+    hipError_t e = if_fir::stream_ctx_open(c, lDevice, ullMaxSamples);
+    if_fir::stream_ctx_alloc_upload(e, &c->d_taps, table.data(), table.size() * sizeof(float));
+    if_fir::stream_ctx_alloc_upload(e, &c->d_twiddle, twiddle.data(), M * sizeof(float2));
+    if_fir::stream_ctx_alloc_upload(e, &c->d_bin_pos, where.data(), bins * sizeof(uint16_t));
+    for (int i = 0; i < 2; i++)
+        if_fir::stream_ctx_alloc_zeroed(e, &c->d_hist[i], hist_bytes);
+    if (e != hipSuccess)
+    {
+        set_err(g_pfb_init_err, "if_fir_pfb_init: %s", hipGetErrorString(e));
+        (void)hipGetLastError();
+        free_ctx(c);
+        return 0;
+    }
+    *ppCtx = c;
+    return 1;
+}
+
+IF_FIR_API void if_fir_pfb_destroy(if_fir_pfb_t *pCtx)
+{
+    free_ctx(pCtx);
+}
+
+IF_FIR_API const char *if_fir_pfb_last_error(const if_fir_pfb_t *pCtx)
+{
+    return pCtx ? pCtx->err : g_pfb_init_err;
+}
+
+// zero both history buffers on the context's stream and wait
+static uint8_t zero_history(if_fir_pfb *c)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    for (int i = 0; i < 2 && c->hist_len > 0; i++)
+        HIP_TRY(c, hipMemsetAsync(c->d_hist[i], 0, (size_t)c->hist_len * sizeof(float2), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 1;
+}
+
+IF_FIR_API uint8_t if_fir_pfb_reset(if_fir_pfb_t *pCtx)
+{
+    if (!pCtx || !zero_history(pCtx))
+        return 0;
+    pCtx->st.position = 0;
+    return 1;
+}
+
+IF_FIR_API uint8_t if_fir_pfb_set_input_format(if_fir_pfb_t *pCtx, uint32_t ulFormat)
+{
+    return if_fir::stream_ctx_set_input_format(pCtx, "if_fir_pfb_set_input_format", ulFormat);
+}
+
+IF_FIR_API uint8_t if_fir_pfb_set_stream(if_fir_pfb_t *pCtx, void *pStream)
+{
+    return if_fir::stream_ctx_set_stream(pCtx, pStream);
+}
+
+IF_FIR_API uint8_t if_fir_pfb_synchronize(if_fir_pfb_t *pCtx)
+{
+    return if_fir::stream_ctx_synchronize(pCtx);
+}
+
+IF_FIR_API uint64_t if_fir_pfb_frame_count(const if_fir_pfb_t *pCtx, uint64_t ullSamples)
+{
+    if_fir::PfbCall call;
+    if (!pCtx || !if_fir::pfb_call(pCtx->st.position, ullSamples, (uint32_t)pCtx->M, (uint32_t)pCtx->D, (uint32_t)pCtx->T, &call))
+        return 0;
+    return call.frames;
+}
+
+static uint8_t run_device(if_fir_pfb *c, const void *in, void *out, uint64_t n, uint64_t *pframes, const char *who)
+{
+    if_fir::PfbCall call;
+    if (!if_fir::stream_ctx_fits(c, who, n))
+        return 0;
+    if (!if_fir::pfb_call(c->st.position, n, (uint32_t)c->M, (uint32_t)c->D, (uint32_t)c->T, &call))
+    {
+        set_err(c->err, "%s: sample count too large: the stream position would pass 2^64", who);
+        return 0;
+    }
+    const uintptr_t in_mask = c->in_i16 ? 3 : 7, out_mask = 7;
+    if (((uintptr_t)in & in_mask) || ((uintptr_t)out & out_mask))
+    {
+        set_err(c->err, "%s: device pointers must be aligned to one sample: %u-byte (input) and %u-byte (output)", who,
+                (unsigned)in_mask + 1, (unsigned)out_mask + 1);
+        return 0;
+    }
+    if ((n && !in) || (call.frames && !out))
+    {
+        set_err(c->err, "%s: NULL device pointer", who);
+        return 0;
+    }
+    if (if_fir::stream_ctx_capturing(c, who))
+        return 0;
+    if (pframes)
+        *pframes = 0;
+    if (n == 0)
+        return 1;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if_fir::PfbArgs a{};
+    a.in = in;
+    a.hist = c->d_hist[c->st.hist_cur];
+    a.hist_out = c->d_hist[c->st.hist_cur ^ 1];
+    a.taps = c->d_taps;
+    a.twiddle = c->d_twiddle;
+    a.bin_pos = c->d_bin_pos;
+    a.out = static_cast<float2 *>(out);
+    a.M = c->M;
+    a.T = c->T;
+    a.K = c->K;
+    a.D = c->D;
+    a.bins = c->bins;
+    a.in_i16 = c->in_i16;
+    a.hist_len = c->hist_len;
+    a.n = (int64_t)n;
+    a.call = call;
+    a.grid_limit = c->grid_limit;
+    a.device = c->device;
+    a.stream = c->stream;
+    HIP_TRY(c, if_fir::launch_pfb(a));
+    c->st.position += n;
+    if (c->hist_len > 0)
+        c->st.hist_cur ^= 1;
+    if (pframes)
+        *pframes = call.frames;
+    return 1;
+}
+
+IF_FIR_API uint8_t if_fir_pfb_process_device(if_fir_pfb_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples, uint64_t *pullFrames)
+{
+    if (!pCtx)
+        return 0;
+    return run_device(pCtx, pDevIn, pDevOut, ullSamples, pullFrames, "if_fir_pfb_process_device");
+}
+
+IF_FIR_API uint8_t if_fir_pfb_process(if_fir_pfb_t *pCtx, const void *pIQIn, float *pfIQOut, uint64_t ullSamples, uint64_t *pullFrames)
+{
+    if (!pCtx)
+        return 0;
+    if (!if_fir::stream_ctx_fits(pCtx, "if_fir_pfb_process", ullSamples))
+        return 0;
+    if_fir::PfbCall call;
+    if (!if_fir::pfb_call(pCtx->st.position, ullSamples, (uint32_t)pCtx->M, (uint32_t)pCtx->D, (uint32_t)pCtx->T, &call))
+    {
+        set_err(pCtx->err, "if_fir_pfb_process: sample count too large: the stream position would pass 2^64");
+        return 0;
+    }
+    if ((ullSamples && !pIQIn) || (call.frames && !pfIQOut))
+    {
+        set_err(pCtx->err, "if_fir_pfb_process: NULL buffer");
+        return 0;
+    }
+    if (pullFrames)
+        *pullFrames = 0;
+    if (ullSamples == 0)
+        return 1;
+    if (!pCtx->d_stage_in)
+    {
+        HIP_TRY(pCtx, hipSetDevice(pCtx->device));
+        // the most frames of a call of ullMaxSamples samples, whatever the position
+        const size_t frames = (size_t)((pCtx->max_samples + (uint64_t)pCtx->D - 1) / (uint64_t)pCtx->D);
+        hipError_t a = hipMalloc(&pCtx->d_stage_out, frames * (size_t)pCtx->bins * sizeof(float2));
+        if (a == hipSuccess)
+            a = hipMalloc(&pCtx->d_stage_in, (size_t)pCtx->max_samples * 8);
+        if (a != hipSuccess)
+        {
+            (void)hipGetLastError();
+            if (pCtx->d_stage_out)
+                (void)hipFree(pCtx->d_stage_out);
+            pCtx->d_stage_out = nullptr;
+            set_err(pCtx->err, "if_fir_pfb_process: staging buffers: %s", hipGetErrorString(a));
+            return 0;
+        }
+    }
+    uint64_t m = 0;
+    if (!if_fir::stream_ctx_staged(
+            pCtx, "if_fir_pfb_process", "frames", pCtx->d_stage_in, pIQIn, ullSamples, &pCtx->st,
+            [&] { return run_device(pCtx, pCtx->d_stage_in, pCtx->d_stage_out, ullSamples, &m, "if_fir_pfb_process"); },
+            [&] {
+                return m ? hipMemcpyAsync(pfIQOut, pCtx->d_stage_out, (size_t)m * (size_t)pCtx->bins * sizeof(float2), hipMemcpyDeviceToHost,
+                                          pCtx->stream)
+                         : hipSuccess;
+            }))
+        return 0;
+    if (pullFrames)
+        *pullFrames = m;
+    return 1;
+}
+
+#ifdef IF_FIR_DEVELOPMENT
+IF_FIR_API uint8_t if_fir_debug_pfb_config(if_fir_pfb_t *pCtx, uint32_t ulGridLimit, uint32_t *pulGroupFrames, uint64_t ullPosition)
+{
+    if (!pCtx)
+        return 0;
+    if (ullPosition != UINT64_MAX)
+    {
+        if (!zero_history(pCtx))
+            return 0;
+        pCtx->st.position = ullPosition;
+    }
+    pCtx->grid_limit = (int)(ulGridLimit > 65536u ? 65536u : ulGridLimit);
+    if (pulGroupFrames)
+        *pulGroupFrames = if_fir::pfb_group_frames((uint32_t)pCtx->M);
+    return 1;
+}
+#endif

@@ -5,7 +5,7 @@
 //
 // psd_chunk_kernel<N, I16>: a WORKGROUP owns whole chunks of up to 8 consecutive segments of one frame (if_fir_psd_plan.h).  Per
 // segment: coalesced global loads (int16 converted on the way, samples before the call from the carried buffer), the window from
-// registers, an in-place decimation-in-frequency transform in LDS (radix-4 passes that meet at workgroup barriers, one last radix-2
+// registers, the in-place decimation-in-frequency transform of if_fir_lds_fft_dev.h in LDS (radix-4 passes that meet at workgroup barriers, one last radix-2
 // pass for N = 512 and 2048; twiddles from a float64-built table staged in LDS once per workgroup), then fma(re, re, im im) of the
 // selected bins only, added in segment order onto per-lane registers.  One float32 chunk sum per selected bin goes to the work buffer.
 // psd_frame_kernel: one thread per (frame, bin) adds the chunk sums in chunk order onto the carried accumulator; a completed frame
@@ -18,63 +18,12 @@
 #include <mutex>
 
 #include "if_fir_kernels.h"
+#include "if_fir_lds_fft_dev.h"
 #include "if_fir_psd.h"
 #include "if_fir_stream_dev.h"
 
 namespace if_fir
 {
-
-__device__ __forceinline__ stream_v2f psd_cmul(const stream_v2f a, const stream_v2f w)
-{
-    return stream_v2f{fmaf(a.x, w.x, -a.y * w.y), fmaf(a.x, w.y, a.y * w.x)};
-}
-
-// one in-place radix-4 decimation-in-frequency pass over sub-blocks of LEN: butterfly j of a sub-block reads and writes the
-// same four places j, j + LEN/4, j + LEN/2, j + 3 LEN/4, so passes only need a barrier between them
-template <int N, int LEN>
-__device__ __forceinline__ void psd_pass4(stream_v2f *__restrict__ x, const stream_v2f *__restrict__ tw, int tid)
-{
-    constexpr int Q = LEN / 4, STEP = N / LEN;
-    for (int b = tid; b < N / 4; b += PSD_THREADS)
-    {
-        const int j = b % Q, base = (b / Q) * LEN + j;
-        const stream_v2f a0 = x[base], a1 = x[base + Q], a2 = x[base + 2 * Q], a3 = x[base + 3 * Q];
-        const stream_v2f t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3, d = a1 - a3;
-        const stream_v2f t3 = {d.y, -d.x}; // -i (a1 - a3)
-        stream_v2f y0 = t0 + t2, y1 = t1 + t3, y2 = t0 - t2, y3 = t1 - t3;
-        if constexpr (Q > 1)
-        {
-            y1 = psd_cmul(y1, tw[j * STEP]);
-            y2 = psd_cmul(y2, tw[2 * j * STEP]);
-            y3 = psd_cmul(y3, tw[3 * j * STEP]);
-        }
-        x[base] = y0;
-        x[base + Q] = y1;
-        x[base + 2 * Q] = y2;
-        x[base + 3 * Q] = y3;
-    }
-}
-
-template <int N, int LEN>
-__device__ __forceinline__ void psd_passes(stream_v2f *__restrict__ x, const stream_v2f *__restrict__ tw, int tid)
-{
-    if constexpr (LEN >= 4)
-    {
-        psd_pass4<N, LEN>(x, tw, tid);
-        __syncthreads();
-        psd_passes<N, LEN / 4>(x, tw, tid);
-    }
-    else if constexpr (LEN == 2)
-    {
-        for (int b = tid; b < N / 2; b += PSD_THREADS)
-        {
-            const stream_v2f a0 = x[2 * b], a1 = x[2 * b + 1];
-            x[2 * b] = a0 + a1;
-            x[2 * b + 1] = a0 - a1;
-        }
-        __syncthreads();
-    }
-}
 
 template <int N, bool I16>
 __global__ __launch_bounds__(PSD_THREADS) void psd_chunk_kernel(const void *__restrict__ in, const float2 *__restrict__ carry,
@@ -119,7 +68,7 @@ __global__ __launch_bounds__(PSD_THREADS) void psd_chunk_kernel(const void *__re
                 x[e] = stream_load<I16>(in, carry, carried, n, first + e) * w[i];
             }
             __syncthreads();
-            psd_passes<N, N>(x, tw, tid);
+            lds_fft_passes<N, N, N, PSD_THREADS>(x, tw, tid);
 #pragma unroll
             for (int i = 0; i < R; i++)
             {
