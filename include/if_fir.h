@@ -567,6 +567,48 @@ uint8_t if_fir_pfb_process(if_fir_pfb_t *pCtx, const void *pIQIn, float *pfIQOut
  * pDevOut holds if_fir_pfb_frame_count() x ulBins samples */
 uint8_t if_fir_pfb_process_device(if_fir_pfb_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples, uint64_t *pullFrames);
 
+/* ---- polyphase synthesis bank (docs/SPEC.md §14; BUILD-DEFINED) ---------------------------------------------------------------
+ * M channel streams on a uniform grid to ONE complex IQ stream in ONE pass (the weighted overlap-add synthesis bank, the
+ * counterpart of if_fir_pfb_t), M = 64 .. 4096.  By definition the sum of M interpolators of SPEC §6 with factor L = ulHop
+ * (1 <= L <= M, any integer), the real prototype h[0..T-1] (T <= 16 M, ceil(T / L) <= 32) and phase word k * 2^32 / M:
+ *     y[n] = sum_k exp(+j 2 pi k n / M) sum_m h[n - m*L] X_k[m],   n = absolute output index since init/reset,   X_k[m<0] = 0
+ * Input is frame-major, the output layout of if_fir_pfb_t: in[m*ulBins + j] = channel (lFirstBin + j) mod M of frame m, complex64
+ * or int16 pairs; channels outside the span are 0.  F frames in give exactly F*L float32 I/Q samples out.
+ * process(a||b) == process(a); process(b), bit for bit, wherever the frames are cut.
+ * The channel combiner (if_fir_combiner_t) stays the route for up to 64 channels at arbitrary centres.
+ * Errors: 0 + if_fir_synth_last_error(); a failed call leaves the context usable and its stream position unchanged.
+ * Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_synth if_fir_synth_t;
+
+typedef struct
+{
+    uint32_t ulChannels; /* M: 64, 128, 256, 512, 1024, 2048 or 4096 */
+    uint32_t ulHop;      /* L: output samples per frame, 1..M */
+    int32_t lFirstBin;   /* first input channel, -M/2 <= lFirstBin < M (negative: counted down from M) */
+    uint32_t ulBins;     /* input channels per frame, 1..M; the span wraps at M */
+} if_fir_synth_config_t;
+
+/* pfTaps: ulTaps real float32 taps, 1 <= ulTaps <= 16 M and ceil(ulTaps / L) <= 32, used as given (no 1/M, no gain of L).
+ * ullMaxFrames: 1..2^32, the most frames of one call */
+uint8_t if_fir_synth_init(if_fir_synth_t **ppCtx, const if_fir_synth_config_t *pCfg, const float *pfTaps, uint32_t ulTaps,
+                          uint64_t ullMaxFrames, int32_t lDevice);
+void if_fir_synth_destroy(if_fir_synth_t *pCtx);
+/* zero the history and the stream position */
+uint8_t if_fir_synth_reset(if_fir_synth_t *pCtx);
+/* IF_FIR_INPUT_F32 or IF_FIR_INPUT_I16 (value = int16 * 2^-15); the history is float32, so a change keeps the stream */
+uint8_t if_fir_synth_set_input_format(if_fir_synth_t *pCtx, uint32_t ulFormat);
+uint8_t if_fir_synth_set_stream(if_fir_synth_t *pCtx, void *pStream);
+uint8_t if_fir_synth_synchronize(if_fir_synth_t *pCtx);
+const char *if_fir_synth_last_error(const if_fir_synth_t *pCtx);
+/* samples a call with ullFrames frames would emit at the current stream position: ullFrames * L (0 when the call would be refused
+ * because its last output index would pass 2^64) */
+uint64_t if_fir_synth_sample_count(const if_fir_synth_t *pCtx, uint64_t ullFrames);
+/* host pointers, synchronous; ullFrames <= ullMaxFrames of init; pFramesIn holds ullFrames x ulBins elements, pfIQOut
+ * if_fir_synth_sample_count() samples; *pullSamples (may be NULL) receives the samples emitted */
+uint8_t if_fir_synth_process(if_fir_synth_t *pCtx, const void *pFramesIn, float *pfIQOut, uint64_t ullFrames, uint64_t *pullSamples);
+/* device pointers aligned to one element (input 8 bytes, 4 for int16; output 8 bytes), asynchronous on the context's stream */
+uint8_t if_fir_synth_process_device(if_fir_synth_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullFrames, uint64_t *pullSamples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,14 @@ uint8_t if_fir_debug_arb_config(if_fir_arb_t *pCtx, uint32_t ulGridLimit, uint32
  * consecutive frames one workgroup owns; an ullPosition other than UINT64_MAX sets the context's absolute sample index (the
  * index of the next call's first sample) and zeroes its history */
 uint8_t if_fir_debug_pfb_config(if_fir_pfb_t *pCtx, uint32_t ulGridLimit, uint32_t *pulGroupFrames, uint64_t ullPosition);
+/* polyphase synthesis bank (if_fir_synth_t): ulGridLimit as if_fir_debug_resamp_config, for every kernel of a call; ulRoute
+ * forces a route from the next call on (0 = the plan's choice, 1 = workspace, 2 = the one-kernel LDS ring, refused where two
+ * workgroups of it do not fit a CU's LDS); *pulRoute (may be NULL) receives the route in use; an ullPosition other than
+ * UINT64_MAX sets the context's absolute FRAME index (the index of the next call's first frame) and zeroes its history */
+uint8_t if_fir_debug_synth_config(if_fir_synth_t *pCtx, uint32_t ulGridLimit, uint32_t ulRoute, uint32_t *pulRoute, uint64_t ullPosition);
+/* ullBytes > 0 replaces the workspace of transformed frames by one of that budget (at least ceil(T / L) frames, at most 2^30
+ * bytes; the default is 128 MB); *pullFrames (may be NULL) receives the frames of a call one chunk then emits the outputs of */
+uint8_t if_fir_debug_synth_workspace(if_fir_synth_t *pCtx, uint64_t ullBytes, uint64_t *pullFrames);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-// if_fir_stream_ctx.h — what the C-ABI shims of the streaming contexts (if_fir_interp_t, if_fir_resamp_t, if_fir_psd_t, if_fir_ddc_t, if_fir_duc_t, if_fir_arb_t, if_fir_pfb_t) share: the base
+// if_fir_stream_ctx.h — what the C-ABI shims of the streaming contexts (if_fir_interp_t, if_fir_resamp_t, if_fir_psd_t, if_fir_ddc_t, if_fir_duc_t, if_fir_arb_t, if_fir_pfb_t, if_fir_synth_t) share: the base
 // of the context struct, the message writer, opening and closing, and the host-pointer ("staged") call.  Host code only.
 //
 // The rule for what belongs here: code in this header never branches on which family calls it.  Where the families differ --

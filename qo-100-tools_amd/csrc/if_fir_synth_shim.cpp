@@ -1,0 +1,385 @@
+// if_fir_synth_shim.cpp — the C ABI of the polyphase synthesis bank (include/if_fir.h, if_fir_synth_*; docs/SPEC.md §14).  Its
+// own opaque context beside the other streaming families.  Same conventions: 1/0 status, a message per context, no CPU fallback.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "if_fir.h"
+#ifdef IF_FIR_DEVELOPMENT
+#include "if_fir_debug.h"
+#endif
+#include "if_fir_stream_ctx.h"
+#include "if_fir_synth.h"
+
+#define IF_FIR_API extern "C" __attribute__((visibility("default")))
+
+// the streaming state: what a call advances (and a failed if_fir_synth_process puts back)
+struct synth_state
+{
+    int hist_cur;
+    uint64_t position;        // input frames since init/reset
+};
+
+struct if_fir_synth : if_fir::StreamCtx
+{
+    int M, T, J, L, first_bin, bins;
+    float *d_taps;            // the table of synth_build_taps
+    float2 *d_twiddle;
+    uint16_t *d_place;
+    float2 *d_hist[2];        // the last J - 1 input frames of the span, float32, ping-pong
+    float2 *d_work;           // work_frames x M transformed frames
+    uint64_t work_frames;
+    synth_state st;
+    void *d_stage_in;         // if_fir_synth_process: staging, allocated by its first call (device-pointer users never pay for it)
+    float2 *d_stage_out;
+    int route;                // SYNTH_ROUTE_WORKSPACE or SYNTH_ROUTE_LDS: the plan's choice unless the development hook forces one
+    int grid_limit;           // development hook
+};
+
+using if_fir::set_err;
+static thread_local char g_synth_init_err[256] = "";
+
+static void free_ctx(if_fir_synth *c)
+{
+    if (!c)
+        return;
+    if_fir::stream_ctx_close(c, {c->d_taps, c->d_twiddle, c->d_place, c->d_hist[0], c->d_hist[1], c->d_work, c->d_stage_in, c->d_stage_out});
+    delete c;
+}
+
+static size_t hist_elems(const if_fir_synth *c)
+{
+    return (size_t)(c->J - 1) * (size_t)c->bins;
+}
+
+// rows of a workspace of `bytes` for this context: no more than its largest call needs
+static uint64_t work_rows(const if_fir_synth *c, uint64_t bytes)
+{
+    const uint64_t rows = if_fir::synth_workspace_frames(bytes, (uint32_t)c->M, (uint32_t)c->J), most = c->max_samples + (uint64_t)c->J - 1;
+    return rows < most ? rows : most;
+}
+
+IF_FIR_API uint8_t if_fir_synth_init(if_fir_synth_t **ppCtx, const if_fir_synth_config_t *pCfg, const float *pfTaps, uint32_t ulTaps,
+                                     uint64_t ullMaxFrames, int32_t lDevice)
+{
+    if (!ppCtx)
+    {
+        set_err(g_synth_init_err, "if_fir_synth_init: ppCtx is NULL");
+        return 0;
+    }
+    *ppCtx = nullptr;
+    if (!pCfg)
+    {
+        set_err(g_synth_init_err, "if_fir_synth_init: pCfg is NULL");
+        return 0;
+    }
+    const uint32_t M = pCfg->ulChannels, L = pCfg->ulHop;
+    if (!if_fir::synth_size_ok(M))
+    {
+        set_err(g_synth_init_err, "if_fir_synth_init: channels must be 64, 128, 256, 512, 1024, 2048 or 4096 (got %u)", M);
+        return 0;
+    }
+    if (!pfTaps || ulTaps < 1 || ulTaps > (uint32_t)if_fir::SYNTH_MAX_ROWS * M)
+    {
+        set_err(g_synth_init_err, "if_fir_synth_init: taps must be 1..%u = 16 x channels (got %u)%s", (uint32_t)if_fir::SYNTH_MAX_ROWS * M,
+                ulTaps, pfTaps ? "" : ", pfTaps is NULL");
+        return 0;
+    }
+    if (L < 1 || L > M)
+    {
+        set_err(g_synth_init_err, "if_fir_synth_init: hop must be 1..%u (got %u)", M, L);
+        return 0;
+    }
+    if (if_fir::synth_terms(ulTaps, L) > (uint32_t)if_fir::SYNTH_MAX_TERMS)
+    {
+        set_err(g_synth_init_err, "if_fir_synth_init: ceil(taps / hop) must be at most %d (got %u taps at hop %u: %u)", if_fir::SYNTH_MAX_TERMS,
+                ulTaps, L, if_fir::synth_terms(ulTaps, L));
+        return 0;
+    }
+    const int64_t half = (int64_t)M / 2, first = pCfg->lFirstBin;
+    if (pCfg->ulBins < 1 || pCfg->ulBins > M || first < -half || first >= (int64_t)M)
+    {
+        set_err(g_synth_init_err, "if_fir_synth_init: the span needs -%lld <= lFirstBin < %u and 1 <= ulBins <= %u (got %d, %u)",
+                (long long)half, M, M, pCfg->lFirstBin, pCfg->ulBins);
+        return 0;
+    }
+    if (ullMaxFrames == 0 || ullMaxFrames > if_fir::SYNTH_MAX_CALL)
+    {
+        set_err(g_synth_init_err, "if_fir_synth_init: ullMaxFrames must be 1..2^32 (got %llu)", (unsigned long long)ullMaxFrames);
+        return 0;
+    }
+    const uint32_t T = ulTaps, J = if_fir::synth_terms(T, L);
+    std::vector<float> table((size_t)J * L);
+    if_fir::synth_build_taps(pfTaps, T, L, table.data());
+    std::vector<float> twiddle(2 * (size_t)M);
+    std::vector<uint16_t> place(M);
+    for (uint32_t t = 0; t < M; t++)
+    {
+        const double ang = -2.0 * M_PI * (double)t / (double)M;
+        twiddle[2 * t] = (float)cos(ang);
+        twiddle[2 * t + 1] = (float)sin(ang);
+        place[t] = (uint16_t)if_fir::synth_slot_place(t, M);
+    }
+
+    if (!if_fir::stream_ctx_device_ok(g_synth_init_err, "if_fir_synth_init", lDevice))
+        return 0;
+    if_fir_synth *c = new (std::nothrow) if_fir_synth();
+    if (!c)
+    {
+        set_err(g_synth_init_err, "if_fir_synth_init: out of host memory");
+        return 0;
+    }
+    c->M = (int)M;
+    c->T = (int)T;
+    c->J = (int)J;
+    c->L = (int)L;
+    c->first_bin = pCfg->lFirstBin;
+    c->bins = (int)pCfg->ulBins;
+    c->route = (int)if_fir::synth_route(M, J, if_fir::SYNTH_ROUTE_PLAN);
+    const size_t hist_bytes = (hist_elems(c) ? hist_elems(c) : 1) * sizeof(float2);
+    hipError_t e = if_fir::stream_ctx_open(c, lDevice, ullMaxFrames);
+    c->work_frames = work_rows(c, if_fir::SYNTH_WORKSPACE_DEFAULT);
+    if_fir::stream_ctx_alloc_upload(e, &c->d_taps, table.data(), table.size() * sizeof(float));
+    if_fir::stream_ctx_alloc_upload(e, &c->d_twiddle, twiddle.data(), M * sizeof(float2));
+    if_fir::stream_ctx_alloc_upload(e, &c->d_place, place.data(), M * sizeof(uint16_t));
+    for (int i = 0; i < 2; i++)
+        if_fir::stream_ctx_alloc_zeroed(e, &c->d_hist[i], hist_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc(&c->d_work, (size_t)c->work_frames * M * sizeof(float2));
+    if (e != hipSuccess)
+    {
+        set_err(g_synth_init_err, "if_fir_synth_init: %s", hipGetErrorString(e));
+        (void)hipGetLastError();
+        free_ctx(c);
+        return 0;
+    }
+    *ppCtx = c;
+    return 1;
+}
+
+IF_FIR_API void if_fir_synth_destroy(if_fir_synth_t *pCtx)
+{
+    free_ctx(pCtx);
+}
+
+IF_FIR_API const char *if_fir_synth_last_error(const if_fir_synth_t *pCtx)
+{
+    return pCtx ? pCtx->err : g_synth_init_err;
+}
+
+// zero both history buffers on the context's stream and wait
+static uint8_t zero_history(if_fir_synth *c)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    for (int i = 0; i < 2 && hist_elems(c) > 0; i++)
+        HIP_TRY(c, hipMemsetAsync(c->d_hist[i], 0, hist_elems(c) * sizeof(float2), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 1;
+}
+
+IF_FIR_API uint8_t if_fir_synth_reset(if_fir_synth_t *pCtx)
+{
+    if (!pCtx || !zero_history(pCtx))
+        return 0;
+    pCtx->st.position = 0;
+    return 1;
+}
+
+IF_FIR_API uint8_t if_fir_synth_set_input_format(if_fir_synth_t *pCtx, uint32_t ulFormat)
+{
+    return if_fir::stream_ctx_set_input_format(pCtx, "if_fir_synth_set_input_format", ulFormat);
+}
+
+IF_FIR_API uint8_t if_fir_synth_set_stream(if_fir_synth_t *pCtx, void *pStream)
+{
+    return if_fir::stream_ctx_set_stream(pCtx, pStream);
+}
+
+IF_FIR_API uint8_t if_fir_synth_synchronize(if_fir_synth_t *pCtx)
+{
+    return if_fir::stream_ctx_synchronize(pCtx);
+}
+
+IF_FIR_API uint64_t if_fir_synth_sample_count(const if_fir_synth_t *pCtx, uint64_t ullFrames)
+{
+    if_fir::SynthCall call;
+    if (!pCtx || !if_fir::synth_call(pCtx->st.position, ullFrames, (uint32_t)pCtx->M, (uint32_t)pCtx->L, (uint32_t)pCtx->T, &call))
+        return 0;
+    return call.outputs;
+}
+
+// the checks of a call that need no device: the frame count against init's and the stream position against 2^64
+static bool plan_call(if_fir_synth *c, const char *who, uint64_t frames, if_fir::SynthCall *call)
+{
+    if (frames > c->max_samples)
+    {
+        set_err(c->err, "%s: %llu frames exceed ullMaxFrames %llu of init", who, (unsigned long long)frames, (unsigned long long)c->max_samples);
+        return false;
+    }
+    if (!if_fir::synth_call(c->st.position, frames, (uint32_t)c->M, (uint32_t)c->L, (uint32_t)c->T, call))
+    {
+        set_err(c->err, "%s: frame count too large: the output position would pass 2^64", who);
+        return false;
+    }
+    return true;
+}
+
+static uint8_t run_device(if_fir_synth *c, const void *in, void *out, uint64_t frames, uint64_t *psamples, const char *who)
+{
+    if_fir::SynthCall call;
+    if (!plan_call(c, who, frames, &call))
+        return 0;
+    const uintptr_t in_mask = c->in_i16 ? 3 : 7, out_mask = 7;
+    if (((uintptr_t)in & in_mask) || ((uintptr_t)out & out_mask))
+    {
+        set_err(c->err, "%s: device pointers must be aligned to one element: %u-byte (input) and %u-byte (output)", who,
+                (unsigned)in_mask + 1, (unsigned)out_mask + 1);
+        return 0;
+    }
+    if (frames && (!in || !out))
+    {
+        set_err(c->err, "%s: NULL device pointer", who);
+        return 0;
+    }
+    if (if_fir::stream_ctx_capturing(c, who))
+        return 0;
+    if (psamples)
+        *psamples = 0;
+    if (frames == 0)
+        return 1;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if_fir::SynthArgs a{};
+    a.in = in;
+    a.hist = c->d_hist[c->st.hist_cur];
+    a.hist_out = c->d_hist[c->st.hist_cur ^ 1];
+    a.taps = c->d_taps;
+    a.twiddle = c->d_twiddle;
+    a.place = c->d_place;
+    a.work = c->d_work;
+    a.out = static_cast<float2 *>(out);
+    a.M = c->M;
+    a.T = c->T;
+    a.J = c->J;
+    a.L = c->L;
+    a.first_bin = c->first_bin;
+    a.bins = c->bins;
+    a.in_i16 = c->in_i16;
+    a.frames = (int64_t)frames;
+    a.work_frames = c->work_frames;
+    a.call = call;
+    a.route = c->route;
+    a.grid_limit = c->grid_limit;
+    a.device = c->device;
+    a.stream = c->stream;
+    HIP_TRY(c, if_fir::launch_synth(a));
+    c->st.position += frames;
+    if (c->J > 1)
+        c->st.hist_cur ^= 1;
+    if (psamples)
+        *psamples = call.outputs;
+    return 1;
+}
+
+IF_FIR_API uint8_t if_fir_synth_process_device(if_fir_synth_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullFrames,
+                                               uint64_t *pullSamples)
+{
+    if (!pCtx)
+        return 0;
+    return run_device(pCtx, pDevIn, pDevOut, ullFrames, pullSamples, "if_fir_synth_process_device");
+}
+
+IF_FIR_API uint8_t if_fir_synth_process(if_fir_synth_t *pCtx, const void *pFramesIn, float *pfIQOut, uint64_t ullFrames, uint64_t *pullSamples)
+{
+    if (!pCtx)
+        return 0;
+    if_fir::SynthCall call;
+    if (!plan_call(pCtx, "if_fir_synth_process", ullFrames, &call))
+        return 0;
+    if (ullFrames && (!pFramesIn || !pfIQOut))
+    {
+        set_err(pCtx->err, "if_fir_synth_process: NULL buffer");
+        return 0;
+    }
+    if (pullSamples)
+        *pullSamples = 0;
+    if (ullFrames == 0)
+        return 1;
+    if (!pCtx->d_stage_in)
+    {
+        HIP_TRY(pCtx, hipSetDevice(pCtx->device));
+        hipError_t a = hipMalloc(&pCtx->d_stage_out, (size_t)pCtx->max_samples * (size_t)pCtx->L * sizeof(float2));
+        if (a == hipSuccess)
+            a = hipMalloc(&pCtx->d_stage_in, (size_t)pCtx->max_samples * (size_t)pCtx->bins * 8);
+        if (a != hipSuccess)
+        {
+            (void)hipGetLastError();
+            if (pCtx->d_stage_out)
+                (void)hipFree(pCtx->d_stage_out);
+            pCtx->d_stage_out = nullptr;
+            set_err(pCtx->err, "if_fir_synth_process: staging buffers: %s", hipGetErrorString(a));
+            return 0;
+        }
+    }
+    uint64_t m = 0;
+    if (!if_fir::stream_ctx_staged_bytes(
+            pCtx, "if_fir_synth_process", "outputs", pCtx->d_stage_in, pFramesIn,
+            (size_t)ullFrames * (size_t)pCtx->bins * (pCtx->in_i16 ? 4 : 8), &pCtx->st,
+            [&] { return run_device(pCtx, pCtx->d_stage_in, pCtx->d_stage_out, ullFrames, &m, "if_fir_synth_process"); },
+            [&] { return hipMemcpyAsync(pfIQOut, pCtx->d_stage_out, (size_t)m * sizeof(float2), hipMemcpyDeviceToHost, pCtx->stream); }))
+        return 0;
+    if (pullSamples)
+        *pullSamples = m;
+    return 1;
+}
+
+#ifdef IF_FIR_DEVELOPMENT
+IF_FIR_API uint8_t if_fir_debug_synth_config(if_fir_synth_t *pCtx, uint32_t ulGridLimit, uint32_t ulRoute, uint32_t *pulRoute,
+                                             uint64_t ullPosition)
+{
+    if (!pCtx)
+        return 0;
+    const uint32_t route = if_fir::synth_route((uint32_t)pCtx->M, (uint32_t)pCtx->J, ulRoute);
+    if (!route)
+    {
+        set_err(pCtx->err, "if_fir_debug_synth_config: route %u is not available here (0 = the plan's choice, 1 = workspace, 2 = LDS ring, "
+                           "which needs 2 x %zu bytes of a CU's LDS for this configuration)", ulRoute,
+                if_fir::synth_lds_route_bytes((uint32_t)pCtx->M, (uint32_t)pCtx->J));
+        return 0;
+    }
+    if (ullPosition != UINT64_MAX)
+    {
+        if (!zero_history(pCtx))
+            return 0;
+        pCtx->st.position = ullPosition;
+    }
+    pCtx->route = (int)route;
+    pCtx->grid_limit = (int)(ulGridLimit > 65536u ? 65536u : ulGridLimit);
+    if (pulRoute)
+        *pulRoute = route;
+    return 1;
+}
+
+IF_FIR_API uint8_t if_fir_debug_synth_workspace(if_fir_synth_t *pCtx, uint64_t ullBytes, uint64_t *pullFrames)
+{
+    if (!pCtx)
+        return 0;
+    if (ullBytes)
+    {
+        const uint64_t rows = work_rows(pCtx, ullBytes);
+        HIP_TRY(pCtx, hipSetDevice(pCtx->device));
+        HIP_TRY(pCtx, hipStreamSynchronize(pCtx->stream));
+        float2 *work = nullptr;
+        HIP_TRY(pCtx, hipMalloc(&work, (size_t)rows * (size_t)pCtx->M * sizeof(float2)));
+        (void)hipFree(pCtx->d_work);
+        pCtx->d_work = work;
+        pCtx->work_frames = rows;
+    }
+    if (pullFrames)
+        *pullFrames = if_fir::synth_chunk_frames(pCtx->work_frames, (uint32_t)pCtx->J);
+    return 1;
+}
+#endif

@@ -54,6 +54,9 @@ EXPORTS = [
     "if_fir_arb_process_device", "if_fir_arb_step_from_rates",
     "if_fir_pfb_init", "if_fir_pfb_destroy", "if_fir_pfb_reset", "if_fir_pfb_set_input_format", "if_fir_pfb_set_stream",
     "if_fir_pfb_synchronize", "if_fir_pfb_last_error", "if_fir_pfb_frame_count", "if_fir_pfb_process", "if_fir_pfb_process_device",
+    "if_fir_synth_init", "if_fir_synth_destroy", "if_fir_synth_reset", "if_fir_synth_set_input_format", "if_fir_synth_set_stream",
+    "if_fir_synth_synchronize", "if_fir_synth_last_error", "if_fir_synth_sample_count", "if_fir_synth_process",
+    "if_fir_synth_process_device",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
@@ -63,7 +66,7 @@ DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_ta
                "if_fir_debug_resamp_config", "if_fir_debug_psd_plan",
                "if_fir_debug_combiner_config", "if_fir_debug_combiner_seek", "if_fir_debug_combiner_tables",
                "if_fir_debug_ddc_config", "if_fir_debug_duc_config", "if_fir_debug_arb_config",
-               "if_fir_debug_pfb_config"]
+               "if_fir_debug_pfb_config", "if_fir_debug_synth_config", "if_fir_debug_synth_workspace"]
 MC_ID_BYTES = 128
 
 
@@ -75,6 +78,11 @@ class PsdConfig(ctypes.Structure):
 
 class PfbConfig(ctypes.Structure):
     """if_fir_pfb_config_t"""
+    _fields_ = [("ulChannels", ctypes.c_uint32), ("ulHop", ctypes.c_uint32), ("lFirstBin", ctypes.c_int32), ("ulBins", ctypes.c_uint32)]
+
+
+class SynthConfig(ctypes.Structure):
+    """if_fir_synth_config_t"""
     _fields_ = [("ulChannels", ctypes.c_uint32), ("ulHop", ctypes.c_uint32), ("lFirstBin", ctypes.c_int32), ("ulBins", ctypes.c_uint32)]
 
 
@@ -189,7 +197,7 @@ def _load(path, dev):
     L.if_fir_mc_get_chunk_samples.restype = u8
     # the streaming contexts (_StreamCtx): what the families declare alike, then what each has of its own
     for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_", "if_fir_ddc_", "if_fir_duc_", "if_fir_arb_",
-                   "if_fir_pfb_"):
+                   "if_fir_pfb_", "if_fir_synth_"):
         for name, args, res in (("destroy", [vp], None), ("reset", [vp], u8), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
                                 ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p)):
             getattr(L, prefix + name).argtypes = args
@@ -262,7 +270,19 @@ def _load(path, dev):
     L.if_fir_pfb_process.restype = u8
     L.if_fir_pfb_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.if_fir_pfb_process_device.restype = u8
+    L.if_fir_synth_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(SynthConfig), f32p, u32, u64, i32]
+    L.if_fir_synth_init.restype = u8
+    L.if_fir_synth_sample_count.argtypes = [vp, u64]
+    L.if_fir_synth_sample_count.restype = u64
+    L.if_fir_synth_process.argtypes = [vp, vp, f32p, u64, ctypes.POINTER(u64)]
+    L.if_fir_synth_process.restype = u8
+    L.if_fir_synth_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.if_fir_synth_process_device.restype = u8
     if dev:
+        L.if_fir_debug_synth_config.argtypes = [vp, u32, u32, ctypes.POINTER(u32), u64]
+        L.if_fir_debug_synth_config.restype = u8
+        L.if_fir_debug_synth_workspace.argtypes = [vp, u64, ctypes.POINTER(u64)]
+        L.if_fir_debug_synth_workspace.restype = u8
         L.if_fir_debug_pfb_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
         L.if_fir_debug_pfb_config.restype = u8
         L.if_fir_debug_combiner_config.argtypes = [vp, u32]
@@ -537,7 +557,7 @@ class IfFir:
 
 
 class _StreamCtx:
-    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb and IfFirPfb share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
+    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb and IfFirSynth share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
     calls the three families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
     __init__, self._L, self._ctx and self._i16."""
     _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
@@ -1152,6 +1172,86 @@ class IfFirPfb(_StreamCtx):
                                                     self.NO_POSITION if position is None else int(position)))
         self._grid_limit = int(grid_limit)
         return int(group.value)
+
+
+class IfFirSynth(_StreamCtx):
+    """One if_fir_synth_t: `channels` channel streams on a uniform grid to one IQ stream in one pass, `hop` output samples per
+    frame of `bins` values (docs/SPEC.md §14).  Methods mirror the C entry points; its input is what IfFirPfb.process returns."""
+    _PREFIX = "if_fir_synth_"
+    NO_POSITION = (1 << 64) - 1
+    ROUTE_PLAN, ROUTE_WORKSPACE, ROUTE_LDS = 0, 1, 2
+
+    def __init__(self, taps, channels, hop=None, first_bin=0, bins=None, max_frames=1 << 12, device=0, dev=False):
+        self._L = dev_lib() if dev else lib()
+        self._ctx = ctypes.c_void_p()
+        self._dev = bool(dev)
+        taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        self.taps = taps
+        self.channels = int(channels)
+        self.hop = self.channels if hop is None else int(hop)
+        self.first_bin = int(first_bin)
+        self.bins = self.channels if bins is None else int(bins)
+        self._i16 = False
+        if not all(0 <= v < 1 << 32 for v in (self.channels, self.hop, self.bins)) or not -(1 << 31) <= self.first_bin < 1 << 31:
+            raise IfFirError("if_fir_synth_init: channels, hop and bins must be unsigned, first_bin a 32-bit integer")
+        cfg = SynthConfig(self.channels, self.hop, self.first_bin, self.bins)
+        if not self._L.if_fir_synth_init(ctypes.byref(self._ctx), ctypes.byref(cfg), _f32p(taps) if taps.size else None, taps.size,
+                                         int(max_frames), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._c("last_error")(None).decode())
+
+    def sample_count(self, frames):
+        """if_fir_synth_sample_count(): output samples of a call with `frames` frames at the current stream position."""
+        return int(self._L.if_fir_synth_sample_count(self._ctx, int(frames)))
+
+    def _frames_input(self, frames):
+        """(contiguous array, frame count) of a host (frames, bins) array: complex64 / interleaved float32, or int16 pairs after
+        set_input_format(INPUT_I16)"""
+        x, n = self._host_input(frames)
+        if n % self.bins:
+            raise IfFirError("if_fir_synth_process: %d elements are not whole frames of %d bins" % (n, self.bins))
+        return x, n // self.bins
+
+    def process(self, frames):
+        """if_fir_synth_process(): a host (frames, bins) array in (what IfFirPfb.process returns); interleaved float32 out."""
+        x, f = self._frames_input(frames)
+        out = np.empty(2 * f * self.hop, dtype=np.float32)
+        m = ctypes.c_uint64(0)
+        dummy = np.zeros(2, dtype=np.float32)
+        self._check(self._L.if_fir_synth_process(self._ctx, ctypes.c_void_p(x.ctypes.data if f else dummy.ctypes.data),
+                                                 _f32p(out if out.size else dummy), f, ctypes.byref(m)))
+        assert m.value * 2 == out.size
+        return out
+
+    def process_device(self, dev_in, dev_out, frames):
+        """if_fir_synth_process_device(): raw device pointers (ints), asynchronous.  Returns the samples emitted."""
+        m = ctypes.c_uint64(0)
+        self._check(self._L.if_fir_synth_process_device(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
+                                                        int(frames), ctypes.byref(m)))
+        return int(m.value)
+
+    def _need_dev(self, name):
+        if not self._dev:
+            raise IfFirError("%s is in the development library only: construct with dev=True" % name)
+
+    def debug_config(self, grid_limit=0, route=0, position=None):
+        """if_fir_debug_synth_config() (development library: construct with dev=True): at most grid_limit workgroups per kernel
+        (0 = the launcher's choice); route 0 = the plan's choice, 1 = workspace, 2 = LDS (refused where it does not fit);
+        position (optional) = the absolute index of the next call's first FRAME, with the history zeroed.  Returns the route in
+        use."""
+        self._need_dev("if_fir_debug_synth_config")
+        got = ctypes.c_uint32(0)
+        self._check(self._L.if_fir_debug_synth_config(self._ctx, int(grid_limit), int(route), ctypes.byref(got),
+                                                      self.NO_POSITION if position is None else int(position)))
+        return int(got.value)
+
+    def debug_workspace(self, nbytes=0):
+        """if_fir_debug_synth_workspace() (development library): nbytes > 0 replaces the workspace by one of that budget.
+        Returns the frames of a call one chunk emits the outputs of."""
+        self._need_dev("if_fir_debug_synth_workspace")
+        got = ctypes.c_uint64(0)
+        self._check(self._L.if_fir_debug_synth_workspace(self._ctx, int(nbytes), ctypes.byref(got)))
+        return int(got.value)
 
 
 FFT_TABLE_FLOATS = 2 * (4096 + 4096 + 256 + 1024 + 1024 + 64 + 256)
