@@ -5,7 +5,6 @@
 
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "if_fir.h"
@@ -30,8 +29,7 @@ struct if_fir_arb : if_fir::StreamCtx
     int T, bits;
     uint64_t step;            // R; set_step changes nothing else
     float *d_taps;            // the pair table (arb_build_taps)
-    float2 *d_hist[2];        // the last hist_len input samples, float32, ping-pong
-    int hist_len;
+    if_fir::StreamHistory hist; // the last K - 1 input samples, float32
     arb_state st;
     void *d_stage_in, *d_stage_out; // if_fir_arb_process
     uint64_t stage_out_cap;   // samples d_stage_out holds: sized for the step of init, grown when a smaller step needs more
@@ -45,7 +43,7 @@ static void free_ctx(if_fir_arb *c)
 {
     if (!c)
         return;
-    if_fir::stream_ctx_close(c, {c->d_taps, c->d_hist[0], c->d_hist[1], c->d_stage_in, c->d_stage_out});
+    if_fir::stream_ctx_close(c, {c->d_taps, c->hist.buf[0], c->hist.buf[1], c->d_stage_in, c->d_stage_out});
     delete c;
 }
 
@@ -68,12 +66,8 @@ IF_FIR_API uint64_t if_fir_arb_step_from_rates(double dRateIn, double dRateOut)
 IF_FIR_API uint8_t if_fir_arb_init(if_fir_arb_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulPhaseBits, uint64_t ullStep,
                                    uint64_t ullMaxSamples, int32_t lDevice)
 {
-    if (!ppCtx)
-    {
-        set_err(g_arb_init_err, "if_fir_arb_init: ppCtx is NULL");
+    if (!if_fir::stream_ctx_init_begin(g_arb_init_err, "if_fir_arb_init", ppCtx))
         return 0;
-    }
-    *ppCtx = nullptr;
     if (!pfTaps || ulTaps == 0 || ulTaps > IF_FIR_ARB_MAX_TAPS)
     {
         set_err(g_arb_init_err, "if_fir_arb_init: taps must be 1..%u (got %u)%s", IF_FIR_ARB_MAX_TAPS, ulTaps, pfTaps ? "" : ", pfTaps is NULL");
@@ -95,40 +89,24 @@ IF_FIR_API uint8_t if_fir_arb_init(if_fir_arb_t **ppCtx, const float *pfTaps, ui
         set_err(g_arb_init_err, "if_fir_arb_init: ullMaxSamples must be 1..2^30 (got %llu)", (unsigned long long)ullMaxSamples);
         return 0;
     }
-    if (!if_fir::stream_ctx_device_ok(g_arb_init_err, "if_fir_arb_init", lDevice))
-        return 0;
-    if_fir_arb *c = new (std::nothrow) if_fir_arb();
+    if_fir_arb *c = if_fir::stream_ctx_new<if_fir_arb>(g_arb_init_err, "if_fir_arb_init", lDevice);
     if (!c)
-    {
-        set_err(g_arb_init_err, "if_fir_arb_init: out of host memory");
         return 0;
-    }
     c->T = (int)ulTaps;
     c->bits = (int)ulPhaseBits;
     c->step = ullStep;
     const if_fir::ArbShape shape = if_fir::arb_shape(c->T, c->bits, c->step);
-    c->hist_len = shape.K - 1;
     std::vector<float> table((size_t)shape.tap_entries * 2);
     if_fir::arb_build_taps(pfTaps, c->T, c->bits, table.data());
-    const size_t hist_bytes = (size_t)(c->hist_len > 0 ? c->hist_len : 1) * sizeof(float2);
     hipError_t e = if_fir::stream_ctx_open(c, lDevice, ullMaxSamples);
     if_fir::stream_ctx_alloc_upload(e, &c->d_taps, table.data(), table.size() * sizeof(float));
-    for (int i = 0; i < 2; i++)
-        if_fir::stream_ctx_alloc_zeroed(e, &c->d_hist[i], hist_bytes);
+    if_fir::stream_history_alloc(e, &c->hist, (size_t)(shape.K - 1) * sizeof(float2), sizeof(float2));
     if (e == hipSuccess)
         e = hipMalloc(&c->d_stage_in, (size_t)ullMaxSamples * 8);
     c->stage_out_cap = max_out(ullMaxSamples, ullStep);
     if (e == hipSuccess)
         e = hipMalloc(&c->d_stage_out, (size_t)c->stage_out_cap * 8);
-    if (e != hipSuccess)
-    {
-        set_err(g_arb_init_err, "if_fir_arb_init: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        free_ctx(c);
-        return 0;
-    }
-    *ppCtx = c;
-    return 1;
+    return if_fir::stream_ctx_init_end(g_arb_init_err, "if_fir_arb_init", e, c, ppCtx, free_ctx);
 }
 
 IF_FIR_API void if_fir_arb_destroy(if_fir_arb_t *pCtx)
@@ -143,12 +121,8 @@ IF_FIR_API const char *if_fir_arb_last_error(const if_fir_arb_t *pCtx)
 
 IF_FIR_API uint8_t if_fir_arb_reset(if_fir_arb_t *pCtx)
 {
-    if (!pCtx)
+    if (!pCtx || !if_fir::stream_history_zero(pCtx, pCtx->hist))
         return 0;
-    HIP_TRY(pCtx, hipSetDevice(pCtx->device));
-    for (int i = 0; i < 2 && pCtx->hist_len > 0; i++)
-        HIP_TRY(pCtx, hipMemsetAsync(pCtx->d_hist[i], 0, (size_t)pCtx->hist_len * sizeof(float2), pCtx->stream));
-    HIP_TRY(pCtx, hipStreamSynchronize(pCtx->stream));
     pCtx->st.consumed = 0;
     pCtx->st.tau = 0;
     return 1;
@@ -198,18 +172,9 @@ static uint8_t run_device(if_fir_arb *c, const void *in, void *out, uint64_t n, 
         set_err(c->err, "%s: sample count too large", who);
         return 0;
     }
-    const uintptr_t in_mask = c->in_i16 ? 3 : 7, out_mask = 7;
-    if (((uintptr_t)in & in_mask) || ((uintptr_t)out & out_mask))
-    {
-        set_err(c->err, "%s: device pointers must be aligned to one sample: %u-byte (input) and %u-byte (output)", who,
-                (unsigned)in_mask + 1, (unsigned)out_mask + 1);
+    if (!if_fir::stream_ctx_aligned(c, who, "sample", in, c->in_i16 ? 3 : 7, out, 7) ||
+        !if_fir::stream_ctx_device_ptrs(c, who, n, in, count, out))
         return 0;
-    }
-    if ((n && !in) || (count && !out))
-    {
-        set_err(c->err, "%s: NULL device pointer", who);
-        return 0;
-    }
     if (if_fir::stream_ctx_capturing(c, who))
         return 0;
     if (n == 0)
@@ -222,8 +187,8 @@ static uint8_t run_device(if_fir_arb *c, const void *in, void *out, uint64_t n, 
     if_fir::ArbArgs a{};
     a.in = in;
     a.out = out;
-    a.hist = c->d_hist[c->st.hist_cur];
-    a.hist_out = c->d_hist[c->st.hist_cur ^ 1];
+    a.hist = c->hist.at<float2>(c->st.hist_cur);
+    a.hist_out = c->hist.at<float2>(c->st.hist_cur ^ 1);
     a.taps = c->d_taps;
     a.T = c->T;
     a.bits = c->bits;
@@ -259,11 +224,8 @@ IF_FIR_API uint8_t if_fir_arb_process(if_fir_arb_t *pCtx, const void *pIQIn, flo
     if (!if_fir::stream_ctx_fits(pCtx, "if_fir_arb_process", ullSamples))
         return 0;
     const uint64_t want = if_fir_arb_out_count(pCtx, ullSamples);
-    if ((ullSamples && !pIQIn) || (want && !pfIQOut))
-    {
-        set_err(pCtx->err, "if_fir_arb_process: NULL buffer");
+    if (!if_fir::stream_ctx_host_ptrs(pCtx, "if_fir_arb_process", ullSamples, pIQIn, want, pfIQOut))
         return 0;
-    }
     if (pullOutSamples)
         *pullOutSamples = 0;
     if (ullSamples == 0)
@@ -302,7 +264,7 @@ IF_FIR_API uint8_t if_fir_debug_arb_config(if_fir_arb_t *pCtx, uint32_t ulGridLi
         set_err(pCtx->err, "if_fir_debug_arb_config: ullTimeOffset must be below 2^34 (got %llu)", (unsigned long long)ullTimeOffset);
         return 0;
     }
-    pCtx->grid_limit = (int)(ulGridLimit > 65536u ? 65536u : ulGridLimit);
+    pCtx->grid_limit = if_fir::stream_ctx_grid_limit(ulGridLimit);
     if (pulTileOutputs)
         *pulTileOutputs = (uint32_t)if_fir::arb_shape(pCtx->T, pCtx->bits, pCtx->step).tile_out;
     if (ullPosition != UINT64_MAX)

@@ -44,7 +44,7 @@ struct if_fir_combiner : if_fir::StreamCtx
     float *d_taps;            // generic kernel: T floats or T (re, im) pairs
     float2 *d_H[2], *d_tw;    // overlap-save: (C + 1) multiply tables of 4096 entries -- table 0 = the plain H, in both images --
                               // and the twiddles (nullptr outside the overlap-save range)
-    float2 *d_hist[2];        // the last hist_len input samples of every channel, float32, ping-pong
+    if_fir::StreamHistory hist; // the last hist_len input samples of every channel (C x hist_len), float32
     int hist_len;
     combiner_state st;
     combiner_plan plan;
@@ -73,7 +73,7 @@ static void free_ctx(if_fir_combiner *c)
 {
     if (!c)
         return;
-    if_fir::stream_ctx_close(c, {c->d_taps, c->d_H[0], c->d_H[1], c->d_tw, c->d_hist[0], c->d_hist[1], c->d_stage_in, c->d_stage_out});
+    if_fir::stream_ctx_close(c, {c->d_taps, c->d_H[0], c->d_H[1], c->d_tw, c->hist.buf[0], c->hist.buf[1], c->d_stage_in, c->d_stage_out});
     delete c;
 }
 
@@ -97,7 +97,7 @@ static bool make_plan(char *err, const char *who, const if_fir_combiner *c, cons
             set_err(err, "%s: centre %d must be within +-0.5 cycles/sample (got %g)", who, ch, f);
             return false;
         }
-        const uint32_t P = (uint32_t)(int64_t)std::llround(f * 4294967296.0); // mod 2^32, as if_fir_interp_set_nco
+        const uint32_t P = if_fir::nco_word_of(f);
         uint32_t G;
         int32_t r;
         if_fir::combiner_split_word(P, &G, &r);
@@ -124,12 +124,8 @@ static bool make_plan(char *err, const char *who, const if_fir_combiner *c, cons
 static uint8_t combiner_init(if_fir_combiner_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulL, uint32_t ulChannels,
                              const double *pdCentre, uint64_t ullMax, int32_t lDevice, int ctaps)
 {
-    if (!ppCtx)
-    {
-        set_err(g_combiner_init_err, "if_fir_combiner_init: ppCtx is NULL");
+    if (!if_fir::stream_ctx_init_begin(g_combiner_init_err, "if_fir_combiner_init", ppCtx))
         return 0;
-    }
-    *ppCtx = nullptr;
     if (!pfTaps || ulTaps == 0 || ulTaps > IF_FIR_MAX_TAPS)
     {
         set_err(g_combiner_init_err, "if_fir_combiner_init: taps must be 1..%u (got %u)%s", IF_FIR_MAX_TAPS, ulTaps, pfTaps ? "" : ", pfTaps is NULL");
@@ -175,8 +171,7 @@ static uint8_t combiner_init(if_fir_combiner_t **ppCtx, const float *pfTaps, uin
     c->hist_len = if_fir::interp_hist_len(c->T, c->L);
     hipError_t e = if_fir::stream_ctx_open(c, lDevice, ullMax);
     if_fir::stream_ctx_alloc_upload(e, &c->d_taps, pfTaps, tap_floats * sizeof(float));
-    for (int i = 0; i < 2; i++)
-        if_fir::stream_ctx_alloc_zeroed(e, &c->d_hist[i], (size_t)c->C * c->hist_len * sizeof(float2));
+    if_fir::stream_history_alloc(e, &c->hist, (size_t)c->C * c->hist_len * sizeof(float2), 0);
     if (e == hipSuccess && if_fir::combiner_fft_supported(c->T, c->L))
     {
         std::vector<float2> tw(if_fir::INTERP_N);
@@ -194,15 +189,7 @@ static uint8_t combiner_init(if_fir_combiner_t **ppCtx, const float *pfTaps, uin
         e = hipMalloc(&c->d_stage_in, stage_pitch(ullMax) * c->C);
     if (e == hipSuccess)
         e = hipMalloc(&c->d_stage_out, (size_t)ullMax * ulL * 8);
-    if (e != hipSuccess)
-    {
-        set_err(g_combiner_init_err, "if_fir_combiner_init: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        free_ctx(c);
-        return 0;
-    }
-    *ppCtx = c;
-    return 1;
+    return if_fir::stream_ctx_init_end(g_combiner_init_err, "if_fir_combiner_init", e, c, ppCtx, free_ctx);
 }
 
 IF_FIR_API uint8_t if_fir_combiner_init(if_fir_combiner_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulInterpolation,
@@ -229,12 +216,8 @@ IF_FIR_API const char *if_fir_combiner_last_error(const if_fir_combiner_t *pCtx)
 
 IF_FIR_API uint8_t if_fir_combiner_reset(if_fir_combiner_t *pCtx)
 {
-    if (!pCtx)
+    if (!pCtx || !if_fir::stream_history_zero(pCtx, pCtx->hist))
         return 0;
-    HIP_TRY(pCtx, hipSetDevice(pCtx->device));
-    for (int i = 0; i < 2; i++)
-        HIP_TRY(pCtx, hipMemsetAsync(pCtx->d_hist[i], 0, (size_t)pCtx->C * pCtx->hist_len * sizeof(float2), pCtx->stream));
-    HIP_TRY(pCtx, hipStreamSynchronize(pCtx->stream));
     pCtx->st.consumed = 0;
     return 1;
 }
@@ -296,7 +279,7 @@ IF_FIR_API uint8_t if_fir_combiner_get_centres(const if_fir_combiner_t *pCtx, do
     if (!pCtx || !pdCentre)
         return 0;
     for (int ch = 0; ch < pCtx->C; ch++)
-        pdCentre[ch] = (double)(int32_t)pCtx->plan.word[ch] / 4294967296.0;
+        pdCentre[ch] = if_fir::nco_freq_of(pCtx->plan.word[ch]);
     return 1;
 }
 
@@ -365,8 +348,8 @@ static uint8_t run_device(if_fir_combiner *c, const void *const *in, void *out, 
     }
     a.C = c->C;
     a.out = out;
-    a.hist = c->d_hist[c->st.hist_cur];
-    a.hist_out = c->d_hist[c->st.hist_cur ^ 1];
+    a.hist = c->hist.at<float2>(c->st.hist_cur);
+    a.hist_out = c->hist.at<float2>(c->st.hist_cur ^ 1);
     a.hist_len = c->hist_len;
     a.H = c->d_H[c->plan.tab_cur];
     a.tw = c->d_tw;
@@ -442,7 +425,7 @@ IF_FIR_API uint8_t if_fir_debug_combiner_config(if_fir_combiner_t *pCtx, uint32_
 {
     if (!pCtx)
         return 0;
-    pCtx->grid_limit = (int)(ulGridLimit > 65536u ? 65536u : ulGridLimit);
+    pCtx->grid_limit = if_fir::stream_ctx_grid_limit(ulGridLimit);
     return 1;
 }
 
@@ -460,7 +443,7 @@ IF_FIR_API uint32_t if_fir_debug_combiner_tables(const float *pfTaps, uint32_t u
     if (!pfTaps || !pulGrid || !plResidual || !pfOut || ulOutFloats < 2u * if_fir::INTERP_N ||
         !if_fir::interp_fft_supported((int)ulTaps, 4) || !std::isfinite(dCentre) || std::fabs(dCentre) > 0.5)
         return 0;
-    if_fir::combiner_split_word((uint32_t)(int64_t)std::llround(dCentre * 4294967296.0), pulGrid, plResidual);
+    if_fir::combiner_split_word(if_fir::nco_word_of(dCentre), pulGrid, plResidual);
     std::vector<float2> H(if_fir::INTERP_N);
     if_fir::combiner_build_table(pfTaps, (int)ulTaps, bComplexTaps ? 1 : 0, *plResidual, H.data());
     memcpy(pfOut, H.data(), H.size() * sizeof(float2));

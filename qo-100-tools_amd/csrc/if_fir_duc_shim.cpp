@@ -5,7 +5,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "if_fir.h"
@@ -32,8 +31,7 @@ struct if_fir_duc : if_fir::StreamCtx
     std::vector<float> h_taps; // as given to init
     uint32_t nco_word;        // SPEC §11 phase word (0 = no mixing)
     float *d_taps;            // the table of duc_build_table for nco_word
-    float2 *d_hist[2];        // the last K - 1 input samples, unrotated float32 I/Q, ping-pong
-    int hist_len;
+    if_fir::StreamHistory hist; // the last K - 1 input samples, unrotated float32 I/Q
     duc_state st;
     void *d_stage_in, *d_stage_out; // if_fir_duc_process
     int grid_limit;           // development hook
@@ -46,7 +44,7 @@ static void free_ctx(if_fir_duc *c)
 {
     if (!c)
         return;
-    if_fir::stream_ctx_close(c, {c->d_taps, c->d_hist[0], c->d_hist[1], c->d_stage_in, c->d_stage_out});
+    if_fir::stream_ctx_close(c, {c->d_taps, c->hist.buf[0], c->hist.buf[1], c->d_stage_in, c->d_stage_out});
     delete c;
 }
 
@@ -62,12 +60,8 @@ static std::vector<float> build_table(const if_fir_duc *c, uint32_t word)
 static uint8_t duc_init(if_fir_duc_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulL, uint64_t ullMax, int32_t lDevice,
                         int ctaps)
 {
-    if (!ppCtx)
-    {
-        set_err(g_duc_init_err, "if_fir_duc_init: ppCtx is NULL");
+    if (!if_fir::stream_ctx_init_begin(g_duc_init_err, "if_fir_duc_init", ppCtx))
         return 0;
-    }
-    *ppCtx = nullptr;
     if (!pfTaps || ulTaps == 0 || ulTaps > IF_FIR_MAX_TAPS)
     {
         set_err(g_duc_init_err, "if_fir_duc_init: taps must be 1..%u (got %u)%s", IF_FIR_MAX_TAPS, ulTaps, pfTaps ? "" : ", pfTaps is NULL");
@@ -89,38 +83,22 @@ static uint8_t duc_init(if_fir_duc_t **ppCtx, const float *pfTaps, uint32_t ulTa
         set_err(g_duc_init_err, "if_fir_duc_init: ullMaxSamples must be 1..2^40 (got %llu)", (unsigned long long)ullMax);
         return 0;
     }
-    if (!if_fir::stream_ctx_device_ok(g_duc_init_err, "if_fir_duc_init", lDevice))
-        return 0;
-    if_fir_duc *c = new (std::nothrow) if_fir_duc();
+    if_fir_duc *c = if_fir::stream_ctx_new<if_fir_duc>(g_duc_init_err, "if_fir_duc_init", lDevice);
     if (!c)
-    {
-        set_err(g_duc_init_err, "if_fir_duc_init: out of host memory");
         return 0;
-    }
     c->T = (int)ulTaps;
     c->L = (int)ulL;
     c->ctaps = ctaps;
     c->h_taps.assign(pfTaps, pfTaps + (size_t)ulTaps * (ctaps ? 2 : 1));
-    c->hist_len = if_fir::duc_phase_taps(c->T, c->L) - 1;
     const std::vector<float> table = build_table(c, 0);
-    const size_t hist_bytes = (size_t)(c->hist_len > 0 ? c->hist_len : 1) * sizeof(float2);
     hipError_t e = if_fir::stream_ctx_open(c, lDevice, ullMax);
     if_fir::stream_ctx_alloc_upload(e, &c->d_taps, table.data(), table.size() * sizeof(float));
-    for (int i = 0; i < 2; i++)
-        if_fir::stream_ctx_alloc_zeroed(e, &c->d_hist[i], hist_bytes);
+    if_fir::stream_history_alloc(e, &c->hist, (size_t)(if_fir::duc_phase_taps(c->T, c->L) - 1) * sizeof(float2), sizeof(float2));
     if (e == hipSuccess)
         e = hipMalloc(&c->d_stage_in, (size_t)ullMax * 8);
     if (e == hipSuccess)
         e = hipMalloc(&c->d_stage_out, (size_t)ullMax * ulL * 4);
-    if (e != hipSuccess)
-    {
-        set_err(g_duc_init_err, "if_fir_duc_init: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        free_ctx(c);
-        return 0;
-    }
-    *ppCtx = c;
-    return 1;
+    return if_fir::stream_ctx_init_end(g_duc_init_err, "if_fir_duc_init", e, c, ppCtx, free_ctx);
 }
 
 IF_FIR_API uint8_t if_fir_duc_init(if_fir_duc_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulInterpolation,
@@ -145,19 +123,9 @@ IF_FIR_API const char *if_fir_duc_last_error(const if_fir_duc_t *pCtx)
     return pCtx ? pCtx->err : g_duc_init_err;
 }
 
-// zero both history buffers on the context's stream and wait
-static uint8_t zero_history(if_fir_duc *c)
-{
-    HIP_TRY(c, hipSetDevice(c->device));
-    for (int i = 0; i < 2 && c->hist_len > 0; i++)
-        HIP_TRY(c, hipMemsetAsync(c->d_hist[i], 0, (size_t)c->hist_len * sizeof(float2), c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return 1;
-}
-
 IF_FIR_API uint8_t if_fir_duc_reset(if_fir_duc_t *pCtx)
 {
-    if (!pCtx || !zero_history(pCtx))
+    if (!pCtx || !if_fir::stream_history_zero(pCtx, pCtx->hist))
         return 0;
     pCtx->st.consumed = 0;
     return 1;
@@ -188,12 +156,9 @@ IF_FIR_API uint8_t if_fir_duc_set_nco(if_fir_duc_t *pCtx, double dFreq)
 {
     if (!pCtx)
         return 0;
-    if (!std::isfinite(dFreq) || std::fabs(dFreq) > 0.5)
-    {
-        set_err(pCtx->err, "if_fir_duc_set_nco: frequency must be within +-0.5 cycles/sample (got %g)", dFreq);
+    uint32_t word;
+    if (!if_fir::stream_ctx_nco_word(pCtx, "if_fir_duc_set_nco", dFreq, &word))
         return 0;
-    }
-    const uint32_t word = (uint32_t)(int64_t)std::llround(dFreq * 4294967296.0); // mod 2^32, as if_fir_set_nco
     if (word == pCtx->nco_word)
         return 1;
     const std::vector<float> table = build_table(pCtx, word);
@@ -208,7 +173,7 @@ IF_FIR_API uint8_t if_fir_duc_get_nco(const if_fir_duc_t *pCtx, double *pdFreq)
 {
     if (!pCtx || !pdFreq)
         return 0;
-    *pdFreq = (double)(int32_t)pCtx->nco_word / 4294967296.0; // the quantised frequency actually applied
+    *pdFreq = if_fir::nco_freq_of(pCtx->nco_word); // the quantised frequency actually applied
     return 1;
 }
 
@@ -243,18 +208,9 @@ static uint8_t run_device(if_fir_duc *c, const void *in, void *out, uint64_t n, 
         set_err(c->err, "%s: the stream position would pass 2^64 outputs", who);
         return 0;
     }
-    const uintptr_t in_mask = c->in_i16 ? 3 : 7, out_mask = c->out_i16 ? 1 : 3;
-    if (((uintptr_t)in & in_mask) || ((uintptr_t)out & out_mask))
-    {
-        set_err(c->err, "%s: device pointers must be aligned to one element: %u-byte (input) and %u-byte (output)", who,
-                (unsigned)in_mask + 1, (unsigned)out_mask + 1);
+    if (!if_fir::stream_ctx_aligned(c, who, "element", in, c->in_i16 ? 3 : 7, out, c->out_i16 ? 1 : 3) ||
+        !if_fir::stream_ctx_device_ptrs(c, who, n, in, n, out))
         return 0;
-    }
-    if (n && (!in || !out))
-    {
-        set_err(c->err, "%s: NULL device pointer", who);
-        return 0;
-    }
     if (if_fir::stream_ctx_capturing(c, who))
         return 0;
     if (n == 0)
@@ -267,8 +223,8 @@ static uint8_t run_device(if_fir_duc *c, const void *in, void *out, uint64_t n, 
     if_fir::DucArgs a{};
     a.in = in;
     a.out = out;
-    a.hist = c->d_hist[c->st.hist_cur];
-    a.hist_out = c->d_hist[c->st.hist_cur ^ 1];
+    a.hist = c->hist.at<float2>(c->st.hist_cur);
+    a.hist_out = c->hist.at<float2>(c->st.hist_cur ^ 1);
     a.taps = c->d_taps;
     a.T = c->T;
     a.L = c->L;
@@ -302,11 +258,8 @@ IF_FIR_API uint8_t if_fir_duc_process(if_fir_duc_t *pCtx, const void *pIQIn, voi
         return 0;
     if (!if_fir::stream_ctx_fits(pCtx, "if_fir_duc_process", ullSamples))
         return 0;
-    if (ullSamples && (!pIQIn || !pOut))
-    {
-        set_err(pCtx->err, "if_fir_duc_process: NULL buffer");
+    if (!if_fir::stream_ctx_host_ptrs(pCtx, "if_fir_duc_process", ullSamples, pIQIn, ullSamples, pOut))
         return 0;
-    }
     if (pullOutSamples)
         *pullOutSamples = 0;
     if (ullSamples == 0)
@@ -330,11 +283,11 @@ IF_FIR_API uint8_t if_fir_debug_duc_config(if_fir_duc_t *pCtx, uint32_t ulGridLi
         return 0;
     if (ullPosition != UINT64_MAX)
     {
-        if (!zero_history(pCtx))
+        if (!if_fir::stream_history_zero(pCtx, pCtx->hist))
             return 0;
         pCtx->st.consumed = ullPosition;
     }
-    pCtx->grid_limit = (int)(ulGridLimit > 65536u ? 65536u : ulGridLimit);
+    pCtx->grid_limit = if_fir::stream_ctx_grid_limit(ulGridLimit);
     if (pulTileInputs)
         *pulTileInputs = (uint32_t)if_fir::duc_shape(pCtx->T, pCtx->L).Q;
     return 1;

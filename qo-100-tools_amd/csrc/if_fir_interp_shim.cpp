@@ -2,10 +2,8 @@
 // opaque context: nothing of if_fir_ctx_t changes.  Same conventions: 1/0 status, a message per context, no CPU fallback.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "if_fir.h"
@@ -31,7 +29,7 @@ struct if_fir_interp : if_fir::StreamCtx
     uint32_t backend_req, backend;
     float *d_taps;            // generic kernel: T floats or T (re, im) pairs
     float2 *d_H, *d_tw;       // overlap-save: the multiply table and the twiddles (nullptr outside its range)
-    float2 *d_hist[2];        // the last hist_len input samples, float32, ping-pong
+    if_fir::StreamHistory hist; // the last hist_len input samples, float32
     int hist_len;
     interp_state st;
     void *d_stage_in, *d_stage_out; // if_fir_interp_process
@@ -53,19 +51,15 @@ static void free_ctx(if_fir_interp *c)
 {
     if (!c)
         return;
-    if_fir::stream_ctx_close(c, {c->d_taps, c->d_H, c->d_tw, c->d_hist[0], c->d_hist[1], c->d_stage_in, c->d_stage_out});
+    if_fir::stream_ctx_close(c, {c->d_taps, c->d_H, c->d_tw, c->hist.buf[0], c->hist.buf[1], c->d_stage_in, c->d_stage_out});
     delete c;
 }
 
 static uint8_t interp_init(if_fir_interp_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulL, uint64_t ullMax,
                            int32_t lDevice, int ctaps)
 {
-    if (!ppCtx)
-    {
-        set_err(g_interp_init_err, "if_fir_interp_init: ppCtx is NULL");
+    if (!if_fir::stream_ctx_init_begin(g_interp_init_err, "if_fir_interp_init", ppCtx))
         return 0;
-    }
-    *ppCtx = nullptr;
     if (!pfTaps || ulTaps == 0 || ulTaps > IF_FIR_MAX_TAPS)
     {
         set_err(g_interp_init_err, "if_fir_interp_init: taps must be 1..%u (got %u)%s", IF_FIR_MAX_TAPS, ulTaps, pfTaps ? "" : ", pfTaps is NULL");
@@ -81,14 +75,9 @@ static uint8_t interp_init(if_fir_interp_t **ppCtx, const float *pfTaps, uint32_
         set_err(g_interp_init_err, "if_fir_interp_init: ullMaxSamples must be 1..2^40/L (got %llu)", (unsigned long long)ullMax);
         return 0;
     }
-    if (!if_fir::stream_ctx_device_ok(g_interp_init_err, "if_fir_interp_init", lDevice))
-        return 0;
-    if_fir_interp *c = new (std::nothrow) if_fir_interp();
+    if_fir_interp *c = if_fir::stream_ctx_new<if_fir_interp>(g_interp_init_err, "if_fir_interp_init", lDevice);
     if (!c)
-    {
-        set_err(g_interp_init_err, "if_fir_interp_init: out of host memory");
         return 0;
-    }
     c->T = (int)ulTaps;
     c->L = (int)ulL;
     c->ctaps = ctaps;
@@ -98,8 +87,7 @@ static uint8_t interp_init(if_fir_interp_t **ppCtx, const float *pfTaps, uint32_
     const size_t tap_floats = (size_t)ulTaps * (ctaps ? 2 : 1);
     hipError_t e = if_fir::stream_ctx_open(c, lDevice, ullMax);
     if_fir::stream_ctx_alloc_upload(e, &c->d_taps, pfTaps, tap_floats * sizeof(float));
-    for (int i = 0; i < 2; i++)
-        if_fir::stream_ctx_alloc_zeroed(e, &c->d_hist[i], (size_t)c->hist_len * sizeof(float2));
+    if_fir::stream_history_alloc(e, &c->hist, (size_t)c->hist_len * sizeof(float2), 0);
     if (e == hipSuccess && if_fir::interp_fft_supported(c->T, c->L))
     {
         std::vector<float2> H(if_fir::INTERP_N), tw(if_fir::INTERP_N);
@@ -111,15 +99,7 @@ static uint8_t interp_init(if_fir_interp_t **ppCtx, const float *pfTaps, uint32_
         e = hipMalloc(&c->d_stage_in, (size_t)ullMax * 8);
     if (e == hipSuccess)
         e = hipMalloc(&c->d_stage_out, (size_t)ullMax * ulL * 8);
-    if (e != hipSuccess)
-    {
-        set_err(g_interp_init_err, "if_fir_interp_init: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        free_ctx(c);
-        return 0;
-    }
-    *ppCtx = c;
-    return 1;
+    return if_fir::stream_ctx_init_end(g_interp_init_err, "if_fir_interp_init", e, c, ppCtx, free_ctx);
 }
 
 IF_FIR_API uint8_t if_fir_interp_init(if_fir_interp_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulInterpolation,
@@ -146,12 +126,8 @@ IF_FIR_API const char *if_fir_interp_last_error(const if_fir_interp_t *pCtx)
 
 IF_FIR_API uint8_t if_fir_interp_reset(if_fir_interp_t *pCtx)
 {
-    if (!pCtx)
+    if (!pCtx || !if_fir::stream_history_zero(pCtx, pCtx->hist))
         return 0;
-    HIP_TRY(pCtx, hipSetDevice(pCtx->device));
-    for (int i = 0; i < 2; i++)
-        HIP_TRY(pCtx, hipMemsetAsync(pCtx->d_hist[i], 0, (size_t)pCtx->hist_len * sizeof(float2), pCtx->stream));
-    HIP_TRY(pCtx, hipStreamSynchronize(pCtx->stream));
     pCtx->st.consumed = 0;
     return 1;
 }
@@ -190,20 +166,14 @@ IF_FIR_API uint8_t if_fir_interp_set_nco(if_fir_interp_t *pCtx, double dFreq)
 {
     if (!pCtx)
         return 0;
-    if (!std::isfinite(dFreq) || std::fabs(dFreq) > 0.5)
-    {
-        set_err(pCtx->err, "if_fir_interp_set_nco: frequency must be within +-0.5 cycles/sample (got %g)", dFreq);
-        return 0;
-    }
-    pCtx->nco_word = (uint32_t)(int64_t)std::llround(dFreq * 4294967296.0); // mod 2^32, as if_fir_set_nco
-    return 1;
+    return if_fir::stream_ctx_nco_word(pCtx, "if_fir_interp_set_nco", dFreq, &pCtx->nco_word);
 }
 
 IF_FIR_API uint8_t if_fir_interp_get_nco(const if_fir_interp_t *pCtx, double *pdFreq)
 {
     if (!pCtx || !pdFreq)
         return 0;
-    *pdFreq = (double)(int32_t)pCtx->nco_word / 4294967296.0;
+    *pdFreq = if_fir::nco_freq_of(pCtx->nco_word);
     return 1;
 }
 
@@ -237,11 +207,8 @@ static uint8_t run_device(if_fir_interp *c, const void *in, void *out, uint64_t 
                 (unsigned)in_mask + 1, (unsigned)out_mask + 1);
         return 0;
     }
-    if (n && (!in || !out))
-    {
-        set_err(c->err, "%s: NULL device pointer", who);
+    if (!if_fir::stream_ctx_device_ptrs(c, who, n, in, n, out))
         return 0;
-    }
     const uint64_t m = n * (uint64_t)c->L;
     if (pout)
         *pout = m;
@@ -253,8 +220,8 @@ static uint8_t run_device(if_fir_interp *c, const void *in, void *out, uint64_t 
     if_fir::InterpArgs a{};
     a.in = in;
     a.out = out;
-    a.hist = c->d_hist[c->st.hist_cur];
-    a.hist_out = c->d_hist[c->st.hist_cur ^ 1];
+    a.hist = c->hist.at<float2>(c->st.hist_cur);
+    a.hist_out = c->hist.at<float2>(c->st.hist_cur ^ 1);
     a.hist_len = c->hist_len;
     a.H = c->d_H;
     a.tw = c->d_tw;
@@ -292,11 +259,8 @@ IF_FIR_API uint8_t if_fir_interp_process(if_fir_interp_t *pCtx, const void *pIQI
         return 0;
     if (!if_fir::stream_ctx_fits(pCtx, "if_fir_interp_process", ullSamples))
         return 0;
-    if (ullSamples && (!pIQIn || !pfIQOut))
-    {
-        set_err(pCtx->err, "if_fir_interp_process: NULL buffer");
+    if (!if_fir::stream_ctx_host_ptrs(pCtx, "if_fir_interp_process", ullSamples, pIQIn, ullSamples, pfIQOut))
         return 0;
-    }
     if (pullOutSamples)
         *pullOutSamples = 0;
     if (ullSamples == 0)
@@ -318,7 +282,7 @@ IF_FIR_API uint8_t if_fir_debug_interp_config(if_fir_interp_t *pCtx, uint32_t bF
     if (!pCtx)
         return 0;
     pCtx->force_full = bForceFull ? 1 : 0;
-    pCtx->grid_limit = (int)(ulGridLimit > 65536u ? 65536u : ulGridLimit);
+    pCtx->grid_limit = if_fir::stream_ctx_grid_limit(ulGridLimit);
     return 1;
 }
 

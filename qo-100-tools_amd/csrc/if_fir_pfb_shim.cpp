@@ -2,10 +2,8 @@
 // opaque context beside the other streaming families.  Same conventions: 1/0 status, a message per context, no CPU fallback.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "if_fir.h"
@@ -30,7 +28,7 @@ struct if_fir_pfb : if_fir::StreamCtx
     float *d_taps;            // the table of pfb_build_taps
     float2 *d_twiddle;
     uint16_t *d_bin_pos;
-    float2 *d_hist[2];        // the last T - 1 input samples, float32, ping-pong
+    if_fir::StreamHistory hist; // the last T - 1 input samples, float32
     int hist_len;
     pfb_state st;
     void *d_stage_in;         // if_fir_pfb_process: staging, allocated by its first call (device-pointer users never pay for it)
@@ -45,19 +43,15 @@ static void free_ctx(if_fir_pfb *c)
 {
     if (!c)
         return;
-    if_fir::stream_ctx_close(c, {c->d_taps, c->d_twiddle, c->d_bin_pos, c->d_hist[0], c->d_hist[1], c->d_stage_in, c->d_stage_out});
+    if_fir::stream_ctx_close(c, {c->d_taps, c->d_twiddle, c->d_bin_pos, c->hist.buf[0], c->hist.buf[1], c->d_stage_in, c->d_stage_out});
     delete c;
 }
 
 IF_FIR_API uint8_t if_fir_pfb_init(if_fir_pfb_t **ppCtx, const if_fir_pfb_config_t *pCfg, const float *pfTaps, uint32_t ulTaps,
                                    uint64_t ullMaxSamples, int32_t lDevice)
 {
-    if (!ppCtx)
-    {
-        set_err(g_pfb_init_err, "if_fir_pfb_init: ppCtx is NULL");
+    if (!if_fir::stream_ctx_init_begin(g_pfb_init_err, "if_fir_pfb_init", ppCtx))
         return 0;
-    }
-    *ppCtx = nullptr;
     if (!pCfg)
     {
         set_err(g_pfb_init_err, "if_fir_pfb_init: pCfg is NULL");
@@ -95,47 +89,26 @@ IF_FIR_API uint8_t if_fir_pfb_init(if_fir_pfb_t **ppCtx, const if_fir_pfb_config
     const uint32_t T = ulTaps, K = if_fir::pfb_rows(T, M), bins = pCfg->ulBins;
     std::vector<float> table((size_t)K * M);
     if_fir::pfb_build_taps(pfTaps, T, M, table.data());
-    std::vector<float> twiddle(2 * (size_t)M);
-    for (uint32_t t = 0; t < M; t++)
-    {
-        const double ang = -2.0 * M_PI * (double)t / (double)M;
-        twiddle[2 * t] = (float)cos(ang);
-        twiddle[2 * t + 1] = (float)sin(ang);
-    }
+    const std::vector<float> twiddle = if_fir::stream_ctx_twiddles(M);
     std::vector<uint16_t> where(bins);
     for (uint32_t j = 0; j < bins; j++)
         where[j] = (uint16_t)if_fir::pfb_bin_place(pCfg->lFirstBin, j, M);
 
-    if (!if_fir::stream_ctx_device_ok(g_pfb_init_err, "if_fir_pfb_init", lDevice))
-        return 0;
-    if_fir_pfb *c = new (std::nothrow) if_fir_pfb();
+    if_fir_pfb *c = if_fir::stream_ctx_new<if_fir_pfb>(g_pfb_init_err, "if_fir_pfb_init", lDevice);
     if (!c)
-    {
-        set_err(g_pfb_init_err, "if_fir_pfb_init: out of host memory");
         return 0;
-    }
     c->M = (int)M;
     c->T = (int)T;
     c->K = (int)K;
     c->D = (int)pCfg->ulHop;
     c->bins = (int)bins;
     c->hist_len = (int)T - 1;
-    const size_t hist_bytes = (size_t)(c->hist_len > 0 ? c->hist_len : 1) * sizeof(float2);
     hipError_t e = if_fir::stream_ctx_open(c, lDevice, ullMaxSamples);
     if_fir::stream_ctx_alloc_upload(e, &c->d_taps, table.data(), table.size() * sizeof(float));
     if_fir::stream_ctx_alloc_upload(e, &c->d_twiddle, twiddle.data(), M * sizeof(float2));
     if_fir::stream_ctx_alloc_upload(e, &c->d_bin_pos, where.data(), bins * sizeof(uint16_t));
-    for (int i = 0; i < 2; i++)
-        if_fir::stream_ctx_alloc_zeroed(e, &c->d_hist[i], hist_bytes);
-    if (e != hipSuccess)
-    {
-        set_err(g_pfb_init_err, "if_fir_pfb_init: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        free_ctx(c);
-        return 0;
-    }
-    *ppCtx = c;
-    return 1;
+    if_fir::stream_history_alloc(e, &c->hist, (size_t)c->hist_len * sizeof(float2), sizeof(float2));
+    return if_fir::stream_ctx_init_end(g_pfb_init_err, "if_fir_pfb_init", e, c, ppCtx, free_ctx);
 }
 
 IF_FIR_API void if_fir_pfb_destroy(if_fir_pfb_t *pCtx)
@@ -148,19 +121,9 @@ IF_FIR_API const char *if_fir_pfb_last_error(const if_fir_pfb_t *pCtx)
     return pCtx ? pCtx->err : g_pfb_init_err;
 }
 
-// zero both history buffers on the context's stream and wait
-static uint8_t zero_history(if_fir_pfb *c)
-{
-    HIP_TRY(c, hipSetDevice(c->device));
-    for (int i = 0; i < 2 && c->hist_len > 0; i++)
-        HIP_TRY(c, hipMemsetAsync(c->d_hist[i], 0, (size_t)c->hist_len * sizeof(float2), c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return 1;
-}
-
 IF_FIR_API uint8_t if_fir_pfb_reset(if_fir_pfb_t *pCtx)
 {
-    if (!pCtx || !zero_history(pCtx))
+    if (!pCtx || !if_fir::stream_history_zero(pCtx, pCtx->hist))
         return 0;
     pCtx->st.position = 0;
     return 1;
@@ -199,18 +162,9 @@ static uint8_t run_device(if_fir_pfb *c, const void *in, void *out, uint64_t n, 
         set_err(c->err, "%s: sample count too large: the stream position would pass 2^64", who);
         return 0;
     }
-    const uintptr_t in_mask = c->in_i16 ? 3 : 7, out_mask = 7;
-    if (((uintptr_t)in & in_mask) || ((uintptr_t)out & out_mask))
-    {
-        set_err(c->err, "%s: device pointers must be aligned to one sample: %u-byte (input) and %u-byte (output)", who,
-                (unsigned)in_mask + 1, (unsigned)out_mask + 1);
+    if (!if_fir::stream_ctx_aligned(c, who, "sample", in, c->in_i16 ? 3 : 7, out, 7) ||
+        !if_fir::stream_ctx_device_ptrs(c, who, n, in, call.frames, out))
         return 0;
-    }
-    if ((n && !in) || (call.frames && !out))
-    {
-        set_err(c->err, "%s: NULL device pointer", who);
-        return 0;
-    }
     if (if_fir::stream_ctx_capturing(c, who))
         return 0;
     if (pframes)
@@ -220,8 +174,8 @@ static uint8_t run_device(if_fir_pfb *c, const void *in, void *out, uint64_t n, 
     HIP_TRY(c, hipSetDevice(c->device));
     if_fir::PfbArgs a{};
     a.in = in;
-    a.hist = c->d_hist[c->st.hist_cur];
-    a.hist_out = c->d_hist[c->st.hist_cur ^ 1];
+    a.hist = c->hist.at<float2>(c->st.hist_cur);
+    a.hist_out = c->hist.at<float2>(c->st.hist_cur ^ 1);
     a.taps = c->d_taps;
     a.twiddle = c->d_twiddle;
     a.bin_pos = c->d_bin_pos;
@@ -266,33 +220,19 @@ IF_FIR_API uint8_t if_fir_pfb_process(if_fir_pfb_t *pCtx, const void *pIQIn, flo
         set_err(pCtx->err, "if_fir_pfb_process: sample count too large: the stream position would pass 2^64");
         return 0;
     }
-    if ((ullSamples && !pIQIn) || (call.frames && !pfIQOut))
-    {
-        set_err(pCtx->err, "if_fir_pfb_process: NULL buffer");
+    if (!if_fir::stream_ctx_host_ptrs(pCtx, "if_fir_pfb_process", ullSamples, pIQIn, call.frames, pfIQOut))
         return 0;
-    }
     if (pullFrames)
         *pullFrames = 0;
     if (ullSamples == 0)
         return 1;
-    if (!pCtx->d_stage_in)
-    {
-        HIP_TRY(pCtx, hipSetDevice(pCtx->device));
-        // the most frames of a call of ullMaxSamples samples, whatever the position
-        const size_t frames = (size_t)((pCtx->max_samples + (uint64_t)pCtx->D - 1) / (uint64_t)pCtx->D);
-        hipError_t a = hipMalloc(&pCtx->d_stage_out, frames * (size_t)pCtx->bins * sizeof(float2));
-        if (a == hipSuccess)
-            a = hipMalloc(&pCtx->d_stage_in, (size_t)pCtx->max_samples * 8);
-        if (a != hipSuccess)
-        {
-            (void)hipGetLastError();
-            if (pCtx->d_stage_out)
-                (void)hipFree(pCtx->d_stage_out);
-            pCtx->d_stage_out = nullptr;
-            set_err(pCtx->err, "if_fir_pfb_process: staging buffers: %s", hipGetErrorString(a));
-            return 0;
-        }
-    }
+    // the most frames of a call of ullMaxSamples samples, whatever the position
+    const size_t frames = (size_t)((pCtx->max_samples + (uint64_t)pCtx->D - 1) / (uint64_t)pCtx->D);
+    if (!pCtx->d_stage_in &&
+        !if_fir::stream_ctx_alloc_staging(pCtx, "if_fir_pfb_process",
+                                          {{(void **)&pCtx->d_stage_out, frames * (size_t)pCtx->bins * sizeof(float2)},
+                                           {&pCtx->d_stage_in, (size_t)pCtx->max_samples * 8}}))
+        return 0;
     uint64_t m = 0;
     if (!if_fir::stream_ctx_staged(
             pCtx, "if_fir_pfb_process", "frames", pCtx->d_stage_in, pIQIn, ullSamples, &pCtx->st,
@@ -315,11 +255,11 @@ IF_FIR_API uint8_t if_fir_debug_pfb_config(if_fir_pfb_t *pCtx, uint32_t ulGridLi
         return 0;
     if (ullPosition != UINT64_MAX)
     {
-        if (!zero_history(pCtx))
+        if (!if_fir::stream_history_zero(pCtx, pCtx->hist))
             return 0;
         pCtx->st.position = ullPosition;
     }
-    pCtx->grid_limit = (int)(ulGridLimit > 65536u ? 65536u : ulGridLimit);
+    pCtx->grid_limit = if_fir::stream_ctx_grid_limit(ulGridLimit);
     if (pulGroupFrames)
         *pulGroupFrames = if_fir::pfb_group_frames((uint32_t)pCtx->M);
     return 1;

@@ -6,7 +6,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "if_fir.h"
@@ -59,12 +58,8 @@ static void free_ctx(if_fir_psd *c)
 IF_FIR_API uint8_t if_fir_psd_init(if_fir_psd_t **ppCtx, const if_fir_psd_config_t *pCfg, const float *pfWindow, uint64_t ullMaxSamples,
                                    int32_t lDevice)
 {
-    if (!ppCtx)
-    {
-        set_err(g_psd_init_err, "if_fir_psd_init: ppCtx is NULL");
+    if (!if_fir::stream_ctx_init_begin(g_psd_init_err, "if_fir_psd_init", ppCtx))
         return 0;
-    }
-    *ppCtx = nullptr;
     if (!pCfg)
     {
         set_err(g_psd_init_err, "if_fir_psd_init: pCfg is NULL");
@@ -141,25 +136,14 @@ IF_FIR_API uint8_t if_fir_psd_init(if_fir_psd_t **ppCtx, const if_fir_psd_config
         set_err(g_psd_init_err, "if_fir_psd_init: the window is all zero");
         return 0;
     }
-    std::vector<float> twiddle(2 * (size_t)N);
-    for (uint32_t t = 0; t < N; t++)
-    {
-        const double ang = -2.0 * M_PI * (double)t / (double)N;
-        twiddle[2 * t] = (float)cos(ang);
-        twiddle[2 * t + 1] = (float)sin(ang);
-    }
+    const std::vector<float> twiddle = if_fir::stream_ctx_twiddles(N);
     std::vector<uint16_t> where(bins);
     for (uint32_t j = 0; j < bins; j++)
         where[j] = (uint16_t)if_fir::psd_bin_position((uint32_t)((first + (int64_t)j + (int64_t)N) % (int64_t)N), N);
 
-    if (!if_fir::stream_ctx_device_ok(g_psd_init_err, "if_fir_psd_init", lDevice))
-        return 0;
-    if_fir_psd *c = new (std::nothrow) if_fir_psd();
+    if_fir_psd *c = if_fir::stream_ctx_new<if_fir_psd>(g_psd_init_err, "if_fir_psd_init", lDevice);
     if (!c)
-    {
-        set_err(g_psd_init_err, "if_fir_psd_init: out of host memory");
         return 0;
-    }
     c->N = (int)N;
     c->H = (int)H;
     c->K = (int)K;
@@ -180,15 +164,7 @@ IF_FIR_API uint8_t if_fir_psd_init(if_fir_psd_t **ppCtx, const if_fir_psd_config
     }
     if (e == hipSuccess)
         e = hipMalloc(&c->d_work, (size_t)work_chunks * bins * sizeof(float));
-    if (e != hipSuccess)
-    {
-        set_err(g_psd_init_err, "if_fir_psd_init: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        free_ctx(c);
-        return 0;
-    }
-    *ppCtx = c;
-    return 1;
+    return if_fir::stream_ctx_init_end(g_psd_init_err, "if_fir_psd_init", e, c, ppCtx, free_ctx);
 }
 
 IF_FIR_API void if_fir_psd_destroy(if_fir_psd_t *pCtx)
@@ -254,11 +230,8 @@ static uint8_t run_device(if_fir_psd *c, const void *in, uint16_t *codes, float 
                 (unsigned)in_mask + 1);
         return 0;
     }
-    if ((n && !in) || (plan.frames && !codes))
-    {
-        set_err(c->err, "%s: NULL device pointer", who);
+    if (!if_fir::stream_ctx_device_ptrs(c, who, n, in, plan.frames, codes))
         return 0;
-    }
     if (if_fir::stream_ctx_capturing(c, who))
         return 0;
     if (pframes)
@@ -318,37 +291,19 @@ IF_FIR_API uint8_t if_fir_psd_process(if_fir_psd_t *pCtx, const void *pIQIn, uin
     if (!if_fir::stream_ctx_fits(pCtx, "if_fir_psd_process", ullSamples))
         return 0;
     const uint64_t want = if_fir_psd_frame_count(pCtx, ullSamples);
-    if ((ullSamples && !pIQIn) || (want && !pusBins))
-    {
-        set_err(pCtx->err, "if_fir_psd_process: NULL buffer");
+    if (!if_fir::stream_ctx_host_ptrs(pCtx, "if_fir_psd_process", ullSamples, pIQIn, want, pusBins))
         return 0;
-    }
     if (pulFrames)
         *pulFrames = 0;
     if (ullSamples == 0)
         return 1;
-    if (!pCtx->d_stage_in)
-    {
-        HIP_TRY(pCtx, hipSetDevice(pCtx->device));
-        const size_t values = (size_t)if_fir::psd_max_frames(pCtx->max_samples, (uint32_t)pCtx->H, (uint32_t)pCtx->K) * (size_t)pCtx->bins;
-        hipError_t a = hipMalloc(&pCtx->d_stage_codes, values * sizeof(uint16_t));
-        if (a == hipSuccess)
-            a = hipMalloc(&pCtx->d_stage_power, values * sizeof(float));
-        if (a == hipSuccess)
-            a = hipMalloc(&pCtx->d_stage_in, (size_t)pCtx->max_samples * 8);
-        if (a != hipSuccess)
-        {
-            (void)hipGetLastError();
-            if (pCtx->d_stage_codes)
-                (void)hipFree(pCtx->d_stage_codes);
-            if (pCtx->d_stage_power)
-                (void)hipFree(pCtx->d_stage_power);
-            pCtx->d_stage_codes = nullptr;
-            pCtx->d_stage_power = nullptr;
-            set_err(pCtx->err, "if_fir_psd_process: staging buffers: %s", hipGetErrorString(a));
-            return 0;
-        }
-    }
+    const size_t values = (size_t)if_fir::psd_max_frames(pCtx->max_samples, (uint32_t)pCtx->H, (uint32_t)pCtx->K) * (size_t)pCtx->bins;
+    if (!pCtx->d_stage_in &&
+        !if_fir::stream_ctx_alloc_staging(pCtx, "if_fir_psd_process",
+                                          {{(void **)&pCtx->d_stage_codes, values * sizeof(uint16_t)},
+                                           {(void **)&pCtx->d_stage_power, values * sizeof(float)},
+                                           {&pCtx->d_stage_in, (size_t)pCtx->max_samples * 8}}))
+        return 0;
     uint32_t m = 0;
     if (!if_fir::stream_ctx_staged(
             pCtx, "if_fir_psd_process", "frames", pCtx->d_stage_in, pIQIn, ullSamples, &pCtx->st,

@@ -4,7 +4,6 @@
 
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "if_fir.h"
@@ -28,8 +27,7 @@ struct if_fir_resamp : if_fir::StreamCtx
     int T, L, M;
     int ctaps;
     float *d_taps;            // the phase-major table (resamp_build_taps)
-    float2 *d_hist[2];        // the last hist_len input samples, float32, ping-pong
-    int hist_len;
+    if_fir::StreamHistory hist; // the last resamp_hist_len input samples, float32
     resamp_state st;
     void *d_stage_in, *d_stage_out; // if_fir_resamp_process
     int grid_limit;           // development hook
@@ -42,7 +40,7 @@ static void free_ctx(if_fir_resamp *c)
 {
     if (!c)
         return;
-    if_fir::stream_ctx_close(c, {c->d_taps, c->d_hist[0], c->d_hist[1], c->d_stage_in, c->d_stage_out});
+    if_fir::stream_ctx_close(c, {c->d_taps, c->hist.buf[0], c->hist.buf[1], c->d_stage_in, c->d_stage_out});
     delete c;
 }
 
@@ -55,12 +53,8 @@ static uint64_t max_out(uint64_t n, uint64_t L, uint64_t M)
 static uint8_t resamp_init(if_fir_resamp_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulL, uint32_t ulM, uint64_t ullMax,
                            int32_t lDevice, int ctaps)
 {
-    if (!ppCtx)
-    {
-        set_err(g_resamp_init_err, "if_fir_resamp_init: ppCtx is NULL");
+    if (!if_fir::stream_ctx_init_begin(g_resamp_init_err, "if_fir_resamp_init", ppCtx))
         return 0;
-    }
-    *ppCtx = nullptr;
     if (!pfTaps || ulTaps == 0 || ulTaps > IF_FIR_MAX_TAPS)
     {
         set_err(g_resamp_init_err, "if_fir_resamp_init: taps must be 1..%u (got %u)%s", IF_FIR_MAX_TAPS, ulTaps, pfTaps ? "" : ", pfTaps is NULL");
@@ -81,40 +75,24 @@ static uint8_t resamp_init(if_fir_resamp_t **ppCtx, const float *pfTaps, uint32_
         set_err(g_resamp_init_err, "if_fir_resamp_init: ullMaxSamples must be 1..2^40/L (got %llu)", (unsigned long long)ullMax);
         return 0;
     }
-    if (!if_fir::stream_ctx_device_ok(g_resamp_init_err, "if_fir_resamp_init", lDevice))
-        return 0;
-    if_fir_resamp *c = new (std::nothrow) if_fir_resamp();
+    if_fir_resamp *c = if_fir::stream_ctx_new<if_fir_resamp>(g_resamp_init_err, "if_fir_resamp_init", lDevice);
     if (!c)
-    {
-        set_err(g_resamp_init_err, "if_fir_resamp_init: out of host memory");
         return 0;
-    }
     c->T = (int)ulTaps;
     c->L = (int)ulL;
     c->M = (int)ulM;
     c->ctaps = ctaps;
-    c->hist_len = if_fir::resamp_hist_len(c->T, c->L);
     const if_fir::ResampShape shape = if_fir::resamp_shape(c->T, c->L, c->M);
     std::vector<float> table((size_t)shape.tap_entries * (ctaps ? 2 : 1));
     if_fir::resamp_build_taps(pfTaps, c->T, ctaps, c->L, table.data());
-    const size_t hist_bytes = (size_t)(c->hist_len > 0 ? c->hist_len : 1) * sizeof(float2);
     hipError_t e = if_fir::stream_ctx_open(c, lDevice, ullMax);
     if_fir::stream_ctx_alloc_upload(e, &c->d_taps, table.data(), table.size() * sizeof(float));
-    for (int i = 0; i < 2; i++)
-        if_fir::stream_ctx_alloc_zeroed(e, &c->d_hist[i], hist_bytes);
+    if_fir::stream_history_alloc(e, &c->hist, (size_t)if_fir::resamp_hist_len(c->T, c->L) * sizeof(float2), sizeof(float2));
     if (e == hipSuccess)
         e = hipMalloc(&c->d_stage_in, (size_t)ullMax * 8);
     if (e == hipSuccess)
         e = hipMalloc(&c->d_stage_out, (size_t)max_out(ullMax, ulL, ulM) * 8);
-    if (e != hipSuccess)
-    {
-        set_err(g_resamp_init_err, "if_fir_resamp_init: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        free_ctx(c);
-        return 0;
-    }
-    *ppCtx = c;
-    return 1;
+    return if_fir::stream_ctx_init_end(g_resamp_init_err, "if_fir_resamp_init", e, c, ppCtx, free_ctx);
 }
 
 IF_FIR_API uint8_t if_fir_resamp_init(if_fir_resamp_t **ppCtx, const float *pfTaps, uint32_t ulTaps, uint32_t ulInterpolation,
@@ -141,12 +119,8 @@ IF_FIR_API const char *if_fir_resamp_last_error(const if_fir_resamp_t *pCtx)
 
 IF_FIR_API uint8_t if_fir_resamp_reset(if_fir_resamp_t *pCtx)
 {
-    if (!pCtx)
+    if (!pCtx || !if_fir::stream_history_zero(pCtx, pCtx->hist))
         return 0;
-    HIP_TRY(pCtx, hipSetDevice(pCtx->device));
-    for (int i = 0; i < 2 && pCtx->hist_len > 0; i++)
-        HIP_TRY(pCtx, hipMemsetAsync(pCtx->d_hist[i], 0, (size_t)pCtx->hist_len * sizeof(float2), pCtx->stream));
-    HIP_TRY(pCtx, hipStreamSynchronize(pCtx->stream));
     pCtx->st.consumed = 0;
     return 1;
 }
@@ -182,18 +156,9 @@ static uint8_t run_device(if_fir_resamp *c, const void *in, void *out, uint64_t 
         set_err(c->err, "%s: sample count too large", who);
         return 0;
     }
-    const uintptr_t in_mask = c->in_i16 ? 3 : 7, out_mask = 7;
-    if (((uintptr_t)in & in_mask) || ((uintptr_t)out & out_mask))
-    {
-        set_err(c->err, "%s: device pointers must be aligned to one sample: %u-byte (input) and %u-byte (output)", who,
-                (unsigned)in_mask + 1, (unsigned)out_mask + 1);
+    if (!if_fir::stream_ctx_aligned(c, who, "sample", in, c->in_i16 ? 3 : 7, out, 7) ||
+        !if_fir::stream_ctx_device_ptrs(c, who, n, in, call.count, out))
         return 0;
-    }
-    if ((n && !in) || (call.count && !out))
-    {
-        set_err(c->err, "%s: NULL device pointer", who);
-        return 0;
-    }
     if (if_fir::stream_ctx_capturing(c, who))
         return 0;
     if (n == 0)
@@ -206,8 +171,8 @@ static uint8_t run_device(if_fir_resamp *c, const void *in, void *out, uint64_t 
     if_fir::ResampArgs a{};
     a.in = in;
     a.out = out;
-    a.hist = c->d_hist[c->st.hist_cur];
-    a.hist_out = c->d_hist[c->st.hist_cur ^ 1];
+    a.hist = c->hist.at<float2>(c->st.hist_cur);
+    a.hist_out = c->hist.at<float2>(c->st.hist_cur ^ 1);
     a.taps = c->d_taps;
     a.T = c->T;
     a.L = c->L;
@@ -244,11 +209,8 @@ IF_FIR_API uint8_t if_fir_resamp_process(if_fir_resamp_t *pCtx, const void *pIQI
     if (!if_fir::stream_ctx_fits(pCtx, "if_fir_resamp_process", ullSamples))
         return 0;
     const uint64_t want = if_fir_resamp_out_count(pCtx, ullSamples);
-    if ((ullSamples && !pIQIn) || (want && !pfIQOut))
-    {
-        set_err(pCtx->err, "if_fir_resamp_process: NULL buffer");
+    if (!if_fir::stream_ctx_host_ptrs(pCtx, "if_fir_resamp_process", ullSamples, pIQIn, want, pfIQOut))
         return 0;
-    }
     if (pullOutSamples)
         *pullOutSamples = 0;
     if (ullSamples == 0)
@@ -269,7 +231,7 @@ IF_FIR_API uint8_t if_fir_debug_resamp_config(if_fir_resamp_t *pCtx, uint32_t ul
 {
     if (!pCtx)
         return 0;
-    pCtx->grid_limit = (int)(ulGridLimit > 65536u ? 65536u : ulGridLimit);
+    pCtx->grid_limit = if_fir::stream_ctx_grid_limit(ulGridLimit);
     if (pulTileOutputs)
         *pulTileOutputs = (uint32_t)if_fir::resamp_shape(pCtx->T, pCtx->L, pCtx->M).tile_out;
     return 1;

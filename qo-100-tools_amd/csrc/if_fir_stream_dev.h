@@ -1,7 +1,7 @@
-// if_fir_stream_dev.h — what the kernel units of the streaming families (interpolator, channel combiner, rational resampler,
-// power spectrum, real-input down-converter, real-output up-converter, arbitrary-ratio resampler, polyphase filter bank, polyphase synthesis bank) share: the device counterpart of if_fir_stream_ctx.h, under the same rule --
-// nothing here branches on which family includes it.  The sample load of a call, the compensated addition, the single-LDS-reads attribute and the launchers'
-// grid sizes.  (ip_load, the interpolator's and the combiner's sample load, is in if_fir_interp_dev.h: DESIGN.md §3.11, Device side.)
+// if_fir_stream_dev.h — what the kernel units of the streaming families (STREAM_FAMILIES in the Makefile) share: the device
+// counterpart of if_fir_stream_ctx.h, under the same rule -- nothing here branches on which family includes it.  The sample load
+// of a call, the compensated addition, the single-LDS-reads attribute and the launchers' grid sizes.
+// (ip_load, the interpolator's and the combiner's sample load, is in if_fir_interp_dev.h: DESIGN.md §3.11, Device side.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

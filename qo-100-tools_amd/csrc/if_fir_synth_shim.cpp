@@ -2,10 +2,8 @@
 // own opaque context beside the other streaming families.  Same conventions: 1/0 status, a message per context, no CPU fallback.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "if_fir.h"
@@ -30,7 +28,7 @@ struct if_fir_synth : if_fir::StreamCtx
     float *d_taps;            // the table of synth_build_taps
     float2 *d_twiddle;
     uint16_t *d_place;
-    float2 *d_hist[2];        // the last J - 1 input frames of the span, float32, ping-pong
+    if_fir::StreamHistory hist; // the last J - 1 input frames of the span, float32
     float2 *d_work;           // work_frames x M transformed frames
     uint64_t work_frames;
     synth_state st;
@@ -47,13 +45,8 @@ static void free_ctx(if_fir_synth *c)
 {
     if (!c)
         return;
-    if_fir::stream_ctx_close(c, {c->d_taps, c->d_twiddle, c->d_place, c->d_hist[0], c->d_hist[1], c->d_work, c->d_stage_in, c->d_stage_out});
+    if_fir::stream_ctx_close(c, {c->d_taps, c->d_twiddle, c->d_place, c->hist.buf[0], c->hist.buf[1], c->d_work, c->d_stage_in, c->d_stage_out});
     delete c;
-}
-
-static size_t hist_elems(const if_fir_synth *c)
-{
-    return (size_t)(c->J - 1) * (size_t)c->bins;
 }
 
 // rows of a workspace of `bytes` for this context: no more than its largest call needs
@@ -66,12 +59,8 @@ static uint64_t work_rows(const if_fir_synth *c, uint64_t bytes)
 IF_FIR_API uint8_t if_fir_synth_init(if_fir_synth_t **ppCtx, const if_fir_synth_config_t *pCfg, const float *pfTaps, uint32_t ulTaps,
                                      uint64_t ullMaxFrames, int32_t lDevice)
 {
-    if (!ppCtx)
-    {
-        set_err(g_synth_init_err, "if_fir_synth_init: ppCtx is NULL");
+    if (!if_fir::stream_ctx_init_begin(g_synth_init_err, "if_fir_synth_init", ppCtx))
         return 0;
-    }
-    *ppCtx = nullptr;
     if (!pCfg)
     {
         set_err(g_synth_init_err, "if_fir_synth_init: pCfg is NULL");
@@ -115,24 +104,14 @@ IF_FIR_API uint8_t if_fir_synth_init(if_fir_synth_t **ppCtx, const if_fir_synth_
     const uint32_t T = ulTaps, J = if_fir::synth_terms(T, L);
     std::vector<float> table((size_t)J * L);
     if_fir::synth_build_taps(pfTaps, T, L, table.data());
-    std::vector<float> twiddle(2 * (size_t)M);
+    const std::vector<float> twiddle = if_fir::stream_ctx_twiddles(M);
     std::vector<uint16_t> place(M);
     for (uint32_t t = 0; t < M; t++)
-    {
-        const double ang = -2.0 * M_PI * (double)t / (double)M;
-        twiddle[2 * t] = (float)cos(ang);
-        twiddle[2 * t + 1] = (float)sin(ang);
         place[t] = (uint16_t)if_fir::synth_slot_place(t, M);
-    }
 
-    if (!if_fir::stream_ctx_device_ok(g_synth_init_err, "if_fir_synth_init", lDevice))
-        return 0;
-    if_fir_synth *c = new (std::nothrow) if_fir_synth();
+    if_fir_synth *c = if_fir::stream_ctx_new<if_fir_synth>(g_synth_init_err, "if_fir_synth_init", lDevice);
     if (!c)
-    {
-        set_err(g_synth_init_err, "if_fir_synth_init: out of host memory");
         return 0;
-    }
     c->M = (int)M;
     c->T = (int)T;
     c->J = (int)J;
@@ -140,25 +119,15 @@ IF_FIR_API uint8_t if_fir_synth_init(if_fir_synth_t **ppCtx, const if_fir_synth_
     c->first_bin = pCfg->lFirstBin;
     c->bins = (int)pCfg->ulBins;
     c->route = (int)if_fir::synth_route(M, J, if_fir::SYNTH_ROUTE_PLAN);
-    const size_t hist_bytes = (hist_elems(c) ? hist_elems(c) : 1) * sizeof(float2);
     hipError_t e = if_fir::stream_ctx_open(c, lDevice, ullMaxFrames);
     c->work_frames = work_rows(c, if_fir::SYNTH_WORKSPACE_DEFAULT);
     if_fir::stream_ctx_alloc_upload(e, &c->d_taps, table.data(), table.size() * sizeof(float));
     if_fir::stream_ctx_alloc_upload(e, &c->d_twiddle, twiddle.data(), M * sizeof(float2));
     if_fir::stream_ctx_alloc_upload(e, &c->d_place, place.data(), M * sizeof(uint16_t));
-    for (int i = 0; i < 2; i++)
-        if_fir::stream_ctx_alloc_zeroed(e, &c->d_hist[i], hist_bytes);
+    if_fir::stream_history_alloc(e, &c->hist, (size_t)(c->J - 1) * (size_t)c->bins * sizeof(float2), sizeof(float2));
     if (e == hipSuccess)
         e = hipMalloc(&c->d_work, (size_t)c->work_frames * M * sizeof(float2));
-    if (e != hipSuccess)
-    {
-        set_err(g_synth_init_err, "if_fir_synth_init: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        free_ctx(c);
-        return 0;
-    }
-    *ppCtx = c;
-    return 1;
+    return if_fir::stream_ctx_init_end(g_synth_init_err, "if_fir_synth_init", e, c, ppCtx, free_ctx);
 }
 
 IF_FIR_API void if_fir_synth_destroy(if_fir_synth_t *pCtx)
@@ -171,19 +140,9 @@ IF_FIR_API const char *if_fir_synth_last_error(const if_fir_synth_t *pCtx)
     return pCtx ? pCtx->err : g_synth_init_err;
 }
 
-// zero both history buffers on the context's stream and wait
-static uint8_t zero_history(if_fir_synth *c)
-{
-    HIP_TRY(c, hipSetDevice(c->device));
-    for (int i = 0; i < 2 && hist_elems(c) > 0; i++)
-        HIP_TRY(c, hipMemsetAsync(c->d_hist[i], 0, hist_elems(c) * sizeof(float2), c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return 1;
-}
-
 IF_FIR_API uint8_t if_fir_synth_reset(if_fir_synth_t *pCtx)
 {
-    if (!pCtx || !zero_history(pCtx))
+    if (!pCtx || !if_fir::stream_history_zero(pCtx, pCtx->hist))
         return 0;
     pCtx->st.position = 0;
     return 1;
@@ -233,18 +192,9 @@ static uint8_t run_device(if_fir_synth *c, const void *in, void *out, uint64_t f
     if_fir::SynthCall call;
     if (!plan_call(c, who, frames, &call))
         return 0;
-    const uintptr_t in_mask = c->in_i16 ? 3 : 7, out_mask = 7;
-    if (((uintptr_t)in & in_mask) || ((uintptr_t)out & out_mask))
-    {
-        set_err(c->err, "%s: device pointers must be aligned to one element: %u-byte (input) and %u-byte (output)", who,
-                (unsigned)in_mask + 1, (unsigned)out_mask + 1);
+    if (!if_fir::stream_ctx_aligned(c, who, "element", in, c->in_i16 ? 3 : 7, out, 7) ||
+        !if_fir::stream_ctx_device_ptrs(c, who, frames, in, frames, out))
         return 0;
-    }
-    if (frames && (!in || !out))
-    {
-        set_err(c->err, "%s: NULL device pointer", who);
-        return 0;
-    }
     if (if_fir::stream_ctx_capturing(c, who))
         return 0;
     if (psamples)
@@ -254,8 +204,8 @@ static uint8_t run_device(if_fir_synth *c, const void *in, void *out, uint64_t f
     HIP_TRY(c, hipSetDevice(c->device));
     if_fir::SynthArgs a{};
     a.in = in;
-    a.hist = c->d_hist[c->st.hist_cur];
-    a.hist_out = c->d_hist[c->st.hist_cur ^ 1];
+    a.hist = c->hist.at<float2>(c->st.hist_cur);
+    a.hist_out = c->hist.at<float2>(c->st.hist_cur ^ 1);
     a.taps = c->d_taps;
     a.twiddle = c->d_twiddle;
     a.place = c->d_place;
@@ -299,31 +249,17 @@ IF_FIR_API uint8_t if_fir_synth_process(if_fir_synth_t *pCtx, const void *pFrame
     if_fir::SynthCall call;
     if (!plan_call(pCtx, "if_fir_synth_process", ullFrames, &call))
         return 0;
-    if (ullFrames && (!pFramesIn || !pfIQOut))
-    {
-        set_err(pCtx->err, "if_fir_synth_process: NULL buffer");
+    if (!if_fir::stream_ctx_host_ptrs(pCtx, "if_fir_synth_process", ullFrames, pFramesIn, ullFrames, pfIQOut))
         return 0;
-    }
     if (pullSamples)
         *pullSamples = 0;
     if (ullFrames == 0)
         return 1;
-    if (!pCtx->d_stage_in)
-    {
-        HIP_TRY(pCtx, hipSetDevice(pCtx->device));
-        hipError_t a = hipMalloc(&pCtx->d_stage_out, (size_t)pCtx->max_samples * (size_t)pCtx->L * sizeof(float2));
-        if (a == hipSuccess)
-            a = hipMalloc(&pCtx->d_stage_in, (size_t)pCtx->max_samples * (size_t)pCtx->bins * 8);
-        if (a != hipSuccess)
-        {
-            (void)hipGetLastError();
-            if (pCtx->d_stage_out)
-                (void)hipFree(pCtx->d_stage_out);
-            pCtx->d_stage_out = nullptr;
-            set_err(pCtx->err, "if_fir_synth_process: staging buffers: %s", hipGetErrorString(a));
-            return 0;
-        }
-    }
+    if (!pCtx->d_stage_in &&
+        !if_fir::stream_ctx_alloc_staging(pCtx, "if_fir_synth_process",
+                                          {{(void **)&pCtx->d_stage_out, (size_t)pCtx->max_samples * (size_t)pCtx->L * sizeof(float2)},
+                                           {&pCtx->d_stage_in, (size_t)pCtx->max_samples * (size_t)pCtx->bins * 8}}))
+        return 0;
     uint64_t m = 0;
     if (!if_fir::stream_ctx_staged_bytes(
             pCtx, "if_fir_synth_process", "outputs", pCtx->d_stage_in, pFramesIn,
@@ -352,12 +288,12 @@ IF_FIR_API uint8_t if_fir_debug_synth_config(if_fir_synth_t *pCtx, uint32_t ulGr
     }
     if (ullPosition != UINT64_MAX)
     {
-        if (!zero_history(pCtx))
+        if (!if_fir::stream_history_zero(pCtx, pCtx->hist))
             return 0;
         pCtx->st.position = ullPosition;
     }
     pCtx->route = (int)route;
-    pCtx->grid_limit = (int)(ulGridLimit > 65536u ? 65536u : ulGridLimit);
+    pCtx->grid_limit = if_fir::stream_ctx_grid_limit(ulGridLimit);
     if (pulRoute)
         *pulRoute = route;
     return 1;
