@@ -55,7 +55,7 @@ __global__ __launch_bounds__(ARB_THREADS) IF_FIR_SINGLE_READS void fir_arb_kerne
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int hist_len = K - 1;
-    if (blockIdx.x == 0)
+    if (blockIdx.x == 0) // (its own loop: through a shared helper it compiles to other code, profiles/stream_plan_ab.txt)
         for (int i = tid; i < hist_len; i += ARB_THREADS)
         {
             const stream_v2f v = stream_load<I16>(in, hist, hist_len, N, N - hist_len + i);
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(ARB_THREADS) IF_FIR_SINGLE_READS void fir_arb_kerne
     stream_v2f *xs = tl + tap_entries;
     for (int i = tid; i < tap_entries; i += ARB_THREADS)
         tl[i] = reinterpret_cast<const stream_v2f *>(taps)[i];
-    const int top = K - ((K - 1) / ARB_SEG) * ARB_SEG; // taps of the highest segment, 1..16
+    const int top = stream_top_segment(K);
 
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x)
     {
@@ -78,27 +78,9 @@ __global__ __launch_bounds__(ARB_THREADS) IF_FIR_SINGLE_READS void fir_arb_kerne
         arb_time(tau_rel, (uint64_t)tile * ARB_TILE_OUT, R, &q0, &f0);
         const int64_t first = q0 - (K - 1); // >= -hist_len
         if (first >= 0 && first + x_len <= N)
-        {
             // the whole window lies inside the call: plain loads
-            if constexpr (I16)
-            {
-                const int *src = static_cast<const int *>(in) + first;
-                for (int s = tid; s < x_len; s += ARB_THREADS)
-                {
-                    const int w = src[s];
-                    xs[s] = stream_v2f{(float)(short)(w & 0xffff) * (1.0f / 32768.0f), (float)(w >> 16) * (1.0f / 32768.0f)};
-                }
-            }
-            else
-            {
-                const float2 *src = static_cast<const float2 *>(in) + first;
-                for (int s = tid; s < x_len; s += ARB_THREADS)
-                {
-                    const float2 v = src[s];
-                    xs[s] = stream_v2f{v.x, v.y};
-                }
-            }
-        }
+            for (int s = tid; s < x_len; s += ARB_THREADS)
+                xs[s] = stream_sample<I16>(in, first + s);
         else
             for (int s = tid; s < x_len; s += ARB_THREADS)
                 xs[s] = stream_load<I16>(in, hist, hist_len, N, first + s);
@@ -123,7 +105,7 @@ __global__ __launch_bounds__(ARB_THREADS) IF_FIR_SINGLE_READS void fir_arb_kerne
             acc_a[k] = lost_a[k] = acc_b[k] = lost_b[k] = stream_v2f{0.f, 0.f};
         // e = K - 1 - j counts up from the oldest sample while j walks down through the segments
         int e = 0;
-        for (int len = top; e < K; len = ARB_SEG)
+        for (int len = top; e < K; len = STREAM_SEG)
         {
             stream_v2f sa[ARB_R], sb[ARB_R];
 #pragma unroll
@@ -162,9 +144,8 @@ __global__ __launch_bounds__(ARB_THREADS) IF_FIR_SINGLE_READS void fir_arb_kerne
 template <bool I16>
 static hipError_t launch_t(const ArbArgs &a)
 {
-    static DeviceSetup setup;
     int cus = 0;
-    const hipError_t e = device_setup(setup, a.device, reinterpret_cast<const void *>(&fir_arb_kernel<I16>), ARB_LDS_MAX, &cus);
+    const hipError_t e = stream_kernel_setup<&fir_arb_kernel<I16>>(a.device, ARB_LDS_MAX, &cus);
     if (e != hipSuccess)
         return e;
     const ArbShape s = arb_shape(a.T, a.bits, a.step);

@@ -15,11 +15,7 @@
 
 #include <cmath>
 
-#if defined(__HIPCC__)
-#define IF_FIR_ARB_HD __host__ __device__
-#else
-#define IF_FIR_ARB_HD
-#endif
+#include "if_fir_stream_plan.h"
 
 namespace if_fir
 {
@@ -35,7 +31,6 @@ constexpr uint64_t ARB_MAX_SAMPLES = (uint64_t)1 << 36; // inputs of one call: 6
 constexpr int ARB_THREADS = 256;                     // one workgroup
 constexpr int ARB_R = 4;                             // outputs per lane: t, t + 256, t + 512, t + 768 of the tile
 constexpr int ARB_TILE_OUT = ARB_THREADS * ARB_R;    // consecutive outputs of one tile
-constexpr int ARB_SEG = 16;                          // taps per accumulation segment (SPEC §7's order)
 
 inline bool arb_valid(uint32_t T, uint32_t b, uint64_t R)
 {
@@ -113,7 +108,7 @@ inline bool arb_state_ok(uint64_t c, arb_u128 tau)
 
 // the time of output i of a call, counted from the call's first input: tau_rel + i R as a 64-bit integer part and a 32-bit
 // fraction.  One 64 x 64 -> 128 multiply; i < 2^43 and R <= 2^34 keep the product below 2^77, so its high word fits 32 bits.
-IF_FIR_ARB_HD inline void arb_time(uint64_t tau_rel, uint64_t i, uint64_t R, int64_t *q, uint32_t *f)
+IF_FIR_STREAM_HD inline void arb_time(uint64_t tau_rel, uint64_t i, uint64_t R, int64_t *q, uint32_t *f)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     uint64_t hi = __umul64hi(i, R);
@@ -131,7 +126,7 @@ IF_FIR_ARB_HD inline void arb_time(uint64_t tau_rel, uint64_t i, uint64_t R, int
 
 // output l of a tile whose base time has the fraction f0: its input index relative to the tile's q0, its phase and the
 // fraction behind the phase, scaled to [0, 1) and rounded ONCE to float32
-IF_FIR_ARB_HD inline void arb_place(uint32_t f0, int l, uint64_t R, int b, int *dq, int *p, float *mu)
+IF_FIR_STREAM_HD inline void arb_place(uint32_t f0, int l, uint64_t R, int b, int *dq, int *p, float *mu)
 {
     const uint64_t t = (uint64_t)f0 + (uint64_t)l * R; // < 2^32 + 1023 2^34
     const uint32_t f = (uint32_t)t;

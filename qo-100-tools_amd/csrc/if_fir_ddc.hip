@@ -83,10 +83,6 @@ __device__ __forceinline__ void ddc_row(const float *__restrict__ x, const float
 
 constexpr int DDC_FILL = 4; // items (4 loads each) a lane has in flight while it fills an interior tile
 
-// a sample of the call as float32 (stream_load_real's conversion)
-__device__ __forceinline__ float ddc_value(float v) { return v; }
-__device__ __forceinline__ float ddc_value(short v) { return (float)v * (1.0f / 32768.0f); }
-
 // (single LDS reads, if_fir_stream_dev.h)
 template <bool I16>
 __global__ __launch_bounds__(DDC_THREADS) IF_FIR_SINGLE_READS void fir_ddc_kernel(const void *__restrict__ in, float2 *__restrict__ out,
@@ -100,7 +96,7 @@ __global__ __launch_bounds__(DDC_THREADS) IF_FIR_SINGLE_READS void fir_ddc_kerne
     float *xs = ddc_xs;
     const int tid = threadIdx.x;
     const int hist_len = T - 1;
-    if (blockIdx.x == 0)
+    if (blockIdx.x == 0) // (its own loop: through a shared helper it compiles to other code, profiles/stream_plan_ab.txt)
         for (int i = tid; i < hist_len; i += DDC_THREADS)
             hist_out[i] = stream_load_real<I16>(in, hist, hist_len, N, N - hist_len + i);
     if ((int64_t)blockIdx.x >= ntiles)
@@ -109,7 +105,7 @@ __global__ __launch_bounds__(DDC_THREADS) IF_FIR_SINGLE_READS void fir_ddc_kerne
     const int64_t tile_in = (int64_t)tile_out * D;
     const bool mine = DDC_R * tid < tile_out;
     const float *xl = xs + DDC_R * tid;
-    const int top = K - ((K - 1) / DDC_SEG) * DDC_SEG; // taps of a long row's first segment: 4, 8, 12 or 16
+    const int top = stream_top_segment(K); // (a long row's first segment: 4, 8, 12 or 16 taps)
 
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x)
     {
@@ -130,7 +126,8 @@ __global__ __launch_bounds__(DDC_THREADS) IF_FIR_SINGLE_READS void fir_ddc_kerne
                     // (past the last item: the last item again, loaded and not stored)
                     const int q = q0 + u * DDC_THREADS < items ? q0 + u * DDC_THREADS : items - 1;
                     const int cq = q / D, row = q - cq * D, at = 4 * cq * D + row;
-                    v[u] = ddc_v4f{ddc_value(src[at]), ddc_value(src[at + D]), ddc_value(src[at + 2 * D]), ddc_value(src[at + 3 * D])};
+                    v[u] = ddc_v4f{stream_sample_real<I16>(src, at), stream_sample_real<I16>(src, at + D), stream_sample_real<I16>(src, at + 2 * D),
+                                   stream_sample_real<I16>(src, at + 3 * D)};
                     to[u] = row * RS + 4 * cq;
                 }
 #pragma unroll
@@ -203,9 +200,8 @@ __global__ __launch_bounds__(DDC_THREADS) IF_FIR_SINGLE_READS void fir_ddc_kerne
 template <bool I16>
 static hipError_t launch_t(const DdcArgs &a)
 {
-    static DeviceSetup setup;
     int cus = 0;
-    const hipError_t e = device_setup(setup, a.device, reinterpret_cast<const void *>(&fir_ddc_kernel<I16>), DDC_LDS_MAX, &cus);
+    const hipError_t e = stream_kernel_setup<&fir_ddc_kernel<I16>>(a.device, DDC_LDS_MAX, &cus);
     if (e != hipSuccess)
         return e;
     const DdcShape s = ddc_shape(a.T, a.D);

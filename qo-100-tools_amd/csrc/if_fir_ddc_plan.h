@@ -10,9 +10,10 @@
 // the tap (rho, j), row D - 1 - rho, column K - 1 - j + i: row R = D - 1 - rho is a K-tap FIR over a contiguous run of its row.
 // K = ceil(T / D) rounded up to a multiple of 4 (the rows are read 16 bytes at a time); taps beyond T are zero.
 #pragma once
-#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "if_fir_stream_plan.h"
 
 namespace if_fir
 {
@@ -21,7 +22,7 @@ constexpr int DDC_MAX_D = 64;
 constexpr int DDC_MAX_TAPS = 4096;
 constexpr int DDC_THREADS = 256;   // one workgroup
 constexpr int DDC_R = 4;           // consecutive outputs per lane
-constexpr int DDC_SEG = 16;        // taps per accumulation segment at most (SPEC §10)
+constexpr int DDC_SEG = STREAM_SEG; // taps per accumulation segment at most (SPEC §10)
 constexpr int DDC_X_MAX = 16384;   // real samples (float) of one tile's window in LDS, row padding included: 64 KB
 
 // taps per phase row: ceil(T / D) rounded up to a multiple of 4
@@ -74,14 +75,10 @@ inline size_t ddc_lds_bytes(const DdcShape &s, int D)
     return (size_t)s.RS * D * 4;
 }
 constexpr int DDC_LDS_MAX = DDC_X_MAX * 4;
-constexpr int DDC_LDS_PER_CU = 160 * 1024; // gfx950
+constexpr int DDC_LDS_PER_CU = STREAM_LDS_PER_CU;
 
-// workgroups of this shape a CU holds at a time: what its LDS fits, at most 8 (32 waves)
-inline int ddc_groups_per_cu(const DdcShape &s, int D)
-{
-    const int fit = (int)((size_t)DDC_LDS_PER_CU / ddc_lds_bytes(s, D));
-    return fit > 8 ? 8 : fit < 1 ? 1 : fit;
-}
+// workgroups of this shape a CU holds at a time
+inline int ddc_groups_per_cu(const DdcShape &s, int D) { return stream_groups_per_cu(ddc_lds_bytes(s, D)); }
 
 struct DdcCall
 {
@@ -90,31 +87,17 @@ struct DdcCall
     uint32_t n0;    // offset of that sample in the call's input, 0 <= n0 < D
 };
 
-// a call with n inputs at stream position c: the outputs at absolute n in [c, c + n) with n mod D == 0.  Nothing overflows short
-// of c + n itself (refused)
+// a call with n inputs at stream position c: the outputs at absolute n in [c, c + n) with n mod D == 0; c + n past 2^64 is refused
 inline bool ddc_call(uint64_t c, uint64_t n, int D, DdcCall *out)
 {
-    if (c + n < c)
+    if (!stream_decim_call(c, n, (uint64_t)D, &out->n0, &out->count))
         return false;
-    const uint64_t uD = (uint64_t)D;
-    out->n0 = (uint32_t)((uD - c % uD) % uD);
-    out->count = n > out->n0 ? (n - out->n0 - 1) / uD + 1 : 0;
     out->first = c + out->n0; // < c + n when count > 0
     return true;
 }
 
-// g[k] = h[k] e^{+j theta k}, theta = 2 pi P / 2^32, in float64 (the phase (P k) mod 2^32 is an exact integer), rounded once;
-// P = 0: g = h.  out holds T (re, im) pairs
-inline void ddc_mix_taps(const float *taps, int T, int ctaps, uint32_t word, float *out)
-{
-    for (int k = 0; k < T; k++)
-    {
-        const double hr = ctaps ? (double)taps[2 * k] : (double)taps[k], hi = ctaps ? (double)taps[2 * k + 1] : 0.0;
-        const double a = 6.283185307179586476925286766559 * ((double)(uint32_t)(word * (uint32_t)k) / 4294967296.0);
-        out[2 * k] = word ? (float)(hr * cos(a) - hi * sin(a)) : (float)hr;
-        out[2 * k + 1] = word ? (float)(hr * sin(a) + hi * cos(a)) : (float)hi;
-    }
-}
+// g[k] = h[k] e^{+j theta k}: out holds T (re, im) pairs
+inline void ddc_mix_taps(const float *taps, int T, int ctaps, uint32_t word, float *out) { stream_mix_taps(taps, T, ctaps, word, out); }
 
 // the table the kernel reads front to back: entry R K + e = g[rho + j D] with rho = D - 1 - R, j = K - 1 - e, zero where
 // rho + j D >= T.  g: T (re, im) pairs; out holds D K pairs

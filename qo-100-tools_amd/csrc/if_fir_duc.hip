@@ -37,26 +37,6 @@ typedef float duc_v4f __attribute__((ext_vector_type(4)));
 
 constexpr int DUC_FILL = 4; // loads a lane has in flight while it fills an interior window
 
-// input sample j of the call (0 <= j < N, not checked) as float32 (I, Q): stream_load's conversion
-template <bool I16>
-__device__ __forceinline__ stream_v2f duc_sample(const void *__restrict__ in, int64_t j)
-{
-    stream_v2f v;
-    if constexpr (I16)
-    {
-        const int w = static_cast<const int *>(in)[j];
-        v.x = (float)(short)(w & 0xffff) * (1.0f / 32768.0f);
-        v.y = (float)(w >> 16) * (1.0f / 32768.0f);
-    }
-    else
-    {
-        const float2 s = static_cast<const float2 *>(in)[j];
-        v.x = s.x;
-        v.y = s.y;
-    }
-    return v;
-}
-
 // x'[n] = x[n] e^{+j theta L n}: the phasor of the exact word (P L n) mod 2^32, n the sample's absolute index (j = its index in
 // the call, negative in the history)
 __device__ __forceinline__ float2 duc_rotate(stream_v2f v, uint32_t nco_on, uint32_t phi0, uint32_t delta, int64_t j)
@@ -82,7 +62,7 @@ __global__ __launch_bounds__(DUC_THREADS) IF_FIR_SINGLE_READS void fir_duc_kerne
     float *stage = duc_lds + 2 * (Q + KP); // the tile's outputs: L rows of RS floats
     const int tid = threadIdx.x;
     const int hist_len = K - 1;
-    if (blockIdx.x == 0)
+    if (blockIdx.x == 0) // (its own loop: through a shared helper it compiles to other code, profiles/stream_plan_ab.txt)
         for (int i = tid; i < hist_len; i += DUC_THREADS)
         {
             const stream_v2f v = stream_load<I16>(in, hist, hist_len, N, N - hist_len + i);
@@ -109,7 +89,7 @@ __global__ __launch_bounds__(DUC_THREADS) IF_FIR_SINGLE_READS void fir_duc_kerne
                 {
                     // (past the last sample: the last one again, loaded and not stored)
                     const int w = w0 + u * DUC_THREADS < W ? w0 + u * DUC_THREADS : W - 1;
-                    v[u] = duc_sample<I16>(in, jfirst + w);
+                    v[u] = stream_sample<I16>(in, jfirst + w);
                 }
 #pragma unroll
                 for (int u = 0; u < DUC_FILL; u++)
@@ -221,9 +201,8 @@ __global__ __launch_bounds__(DUC_THREADS) IF_FIR_SINGLE_READS void fir_duc_kerne
 template <bool I16, bool O16>
 static hipError_t launch_t(const DucArgs &a)
 {
-    static DeviceSetup setup;
     int cus = 0;
-    const hipError_t e = device_setup(setup, a.device, reinterpret_cast<const void *>(&fir_duc_kernel<I16, O16>), DUC_LDS_MAX, &cus);
+    const hipError_t e = stream_kernel_setup<&fir_duc_kernel<I16, O16>>(a.device, DUC_LDS_MAX, &cus);
     if (e != hipSuccess)
         return e;
     const DucShape s = duc_shape(a.T, a.L);

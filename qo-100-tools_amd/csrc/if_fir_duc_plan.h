@@ -14,11 +14,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define DUC_HOST_DEVICE __host__ __device__
-#else
-#define DUC_HOST_DEVICE
-#endif
+#include "if_fir_stream_plan.h"
 
 namespace if_fir
 {
@@ -28,7 +24,7 @@ constexpr int DUC_MAX_TAPS = 4096;
 constexpr int DUC_THREADS = 256;     // one workgroup: 4 waves
 constexpr int DUC_R = 4;             // consecutive input positions q per lane: a wave covers DUC_RUN of one phase
 constexpr int DUC_RUN = 64 * DUC_R;  // 256
-constexpr int DUC_SEG = 16;          // phase taps per accumulation segment at most (SPEC §7, §11)
+constexpr int DUC_SEG = STREAM_SEG;  // phase taps per accumulation segment at most (SPEC §7, §11)
 constexpr int DUC_TILE_OUT_MAX = 16384; // outputs of one tile at most (their staging area: 64 KB of float32)
 constexpr int DUC_Q_MAX = 1024;
 constexpr int DUC_DIV_SHIFT = 20;    // a tile's output index n < 16384 over L <= 64: n / L = (n duc_div_magic(L)) >> 20
@@ -68,7 +64,7 @@ inline DucShape duc_shape(int T, int L)
     DucShape s;
     s.K = duc_phase_taps(T, L);
     s.KP = duc_row_taps(T, L);
-    s.top = s.K - ((s.K - 1) / DUC_SEG) * DUC_SEG + (s.KP - s.K);
+    s.top = stream_top_segment(s.K) + (s.KP - s.K);
     int runs = DUC_TILE_OUT_MAX / (DUC_RUN * L); // >= 1
     if (runs > DUC_Q_MAX / DUC_RUN)
         runs = DUC_Q_MAX / DUC_RUN;
@@ -88,14 +84,10 @@ inline size_t duc_lds_bytes(const DucShape &s, int L)
 }
 // an upper bound for every shape (the longest window and the largest staging area do not occur together)
 constexpr int DUC_LDS_MAX = (2 * (DUC_Q_MAX + DUC_MAX_TAPS) + (DUC_RUN + 4) * DUC_MAX_L) * 4;
-constexpr int DUC_LDS_PER_CU = 160 * 1024; // gfx950
+constexpr int DUC_LDS_PER_CU = STREAM_LDS_PER_CU;
 
-// workgroups of this shape a CU holds at a time: what its LDS fits, at most 8 (32 waves)
-inline int duc_groups_per_cu(const DucShape &s, int L)
-{
-    const int fit = (int)((size_t)DUC_LDS_PER_CU / duc_lds_bytes(s, L));
-    return fit > 8 ? 8 : fit < 1 ? 1 : fit;
-}
+// workgroups of this shape a CU holds at a time
+inline int duc_groups_per_cu(const DucShape &s, int L) { return stream_groups_per_cu(duc_lds_bytes(s, L)); }
 
 // a call with n inputs at stream position c (inputs since init/reset) emits the n L outputs from c L on; refused when
 // (c + n) L does not fit 64 bits
@@ -107,17 +99,13 @@ inline bool duc_call(uint64_t c, uint64_t n, int L, uint64_t *count)
     return true;
 }
 
-// g[k] = h[k] e^{+j theta k}, theta = 2 pi P / 2^32, in float64 (the phase (P k) mod 2^32 is an exact integer), rounded once and
-// stored as (g_r, -g_i); P = 0: (h_r, -h_i).  out holds T pairs
+// g[k] = h[k] e^{+j theta k} stored as (g_r, -g_i) (the negation is exact: stream_mix_taps has rounded already); P = 0:
+// (h_r, -h_i).  out holds T pairs
 inline void duc_mix_taps(const float *taps, int T, int ctaps, uint32_t word, float *out)
 {
+    stream_mix_taps(taps, T, ctaps, word, out);
     for (int k = 0; k < T; k++)
-    {
-        const double hr = ctaps ? (double)taps[2 * k] : (double)taps[k], hi = ctaps ? (double)taps[2 * k + 1] : 0.0;
-        const double a = 6.283185307179586476925286766559 * ((double)(uint32_t)(word * (uint32_t)k) / 4294967296.0);
-        out[2 * k] = word ? (float)(hr * cos(a) - hi * sin(a)) : (float)hr;
-        out[2 * k + 1] = -(word ? (float)(hr * sin(a) + hi * cos(a)) : (float)hi);
-    }
+        out[2 * k + 1] = -out[2 * k + 1];
 }
 
 // the table the kernel reads front to back: entry p KP + e = the pair of the tap p + j L with j = KP - 1 - e, zero where
@@ -137,7 +125,7 @@ inline void duc_build_table(const float *g, int T, int L, float *out)
 
 // output sample in float32 to int16 (SPEC §11): times 2^15 (exact), to nearest even, saturated (not a number: 0); the kernel
 // calls this very function
-DUC_HOST_DEVICE inline int16_t duc_to_i16(float v)
+IF_FIR_STREAM_HD inline int16_t duc_to_i16(float v)
 {
     const float s = nearbyintf(v * 32768.0f);
     return (int16_t)(s < -32768.0f ? -32768.0f : s > 32767.0f ? 32767.0f : s == s ? s : 0.0f);

@@ -105,7 +105,7 @@ template <bool I16>
 __global__ __launch_bounds__(PFB_THREADS) void pfb_carry_kernel(const void *__restrict__ in, const float2 *__restrict__ hist,
                                                                 float2 *__restrict__ hist_out, int64_t hist_len, int64_t n)
 {
-    // the last hist_len samples of (hist || call)
+    // the last hist_len samples of (hist || call) (its own loop: through a shared helper it compiles to other code, profiles/stream_plan_ab.txt)
     for (int64_t i = (int64_t)blockIdx.x * PFB_THREADS + threadIdx.x; i < hist_len; i += (int64_t)gridDim.x * PFB_THREADS)
     {
         const stream_v2f v = stream_load<I16>(in, hist, hist_len, n, n - hist_len + i);
@@ -116,10 +116,9 @@ __global__ __launch_bounds__(PFB_THREADS) void pfb_carry_kernel(const void *__re
 template <int M, bool I16>
 static hipError_t launch_frames(const PfbArgs &a)
 {
-    static DeviceSetup setup;
     int cus = 0;
     constexpr int lds = (int)pfb_lds_bytes(M);
-    const hipError_t e = device_setup(setup, a.device, reinterpret_cast<const void *>(&pfb_kernel<M, I16>), lds, &cus);
+    const hipError_t e = stream_kernel_setup<&pfb_kernel<M, I16>>(a.device, lds, &cus);
     if (e != hipSuccess)
         return e;
     const unsigned groups = stream_persistent_groups(cus, pfb_groups_per_cu(M), (int64_t)a.call.groups, a.grid_limit);

@@ -21,13 +21,10 @@ constexpr int PFB_THREADS = 256;        // one workgroup
 constexpr int PFB_MIN_M = 64;
 constexpr int PFB_MAX_M = 4096;
 constexpr int PFB_MAX_ROWS = 16;        // K = ceil(T / M)
-constexpr int PFB_BATCH_POINTS = 1024;  // a workgroup transforms at least this many points at a time: 1024 / M frames when M < 1024
+constexpr int PFB_BATCH_POINTS = STREAM_BANK_POINTS; // a workgroup transforms at least this many points at a time
 constexpr uint64_t PFB_MAX_CALL = (uint64_t)1 << 40; // samples of one call
 
-inline bool pfb_size_ok(uint32_t M)
-{
-    return M == 64 || M == 128 || M == 256 || M == 512 || M == 1024 || M == 2048 || M == 4096;
-}
+inline bool pfb_size_ok(uint32_t M) { return stream_size_ok(M, PFB_MIN_M); }
 
 // rows of the tap table: K = ceil(T / M)
 inline uint32_t pfb_rows(uint32_t T, uint32_t M)
@@ -35,11 +32,8 @@ inline uint32_t pfb_rows(uint32_t T, uint32_t M)
     return (T + M - 1) / M;
 }
 
-// frames a workgroup folds and transforms together (every lane of the 256 has a butterfly in every pass)
-constexpr uint32_t pfb_batch(uint32_t M)
-{
-    return M >= (uint32_t)PFB_BATCH_POINTS ? 1u : (uint32_t)PFB_BATCH_POINTS / M;
-}
+// frames a workgroup folds and transforms together
+constexpr uint32_t pfb_batch(uint32_t M) { return stream_bank_batch(M); }
 
 // consecutive frames one workgroup owns: whole batches, at least 8 frames (consecutive frames read overlapping inputs)
 constexpr uint32_t pfb_group_frames(uint32_t M)
@@ -60,11 +54,8 @@ struct PfbCall
 // (refused)
 inline bool pfb_call(uint64_t c, uint64_t n, uint32_t M, uint32_t D, uint32_t T, PfbCall *out)
 {
-    if (c + n < c || D == 0 || M == 0 || T == 0)
+    if (D == 0 || M == 0 || T == 0 || !stream_decim_call(c, n, D, &out->n0, &out->frames))
         return false;
-    const uint64_t uD = D;
-    out->n0 = (uint32_t)((uD - c % uD) % uD);
-    out->frames = n > out->n0 ? (n - out->n0 - 1) / uD + 1 : 0;
     const uint64_t gf = pfb_group_frames(M);
     out->groups = out->frames / gf + (out->frames % gf ? 1 : 0);
     out->cmod = (uint32_t)(c % M);
@@ -95,17 +86,11 @@ inline uint32_t pfb_bin_place(int32_t first_bin, uint32_t j, uint32_t M)
     return psd_bin_position(pfb_bin_channel(first_bin, j, M), M);
 }
 
-// LDS of one workgroup: the batch's points, the twiddles (float2 each) and the bin places (uint16)
-constexpr size_t pfb_lds_bytes(uint32_t M)
-{
-    return (size_t)pfb_batch(M) * M * 8 + (size_t)M * 8 + (size_t)M * 2;
-}
-constexpr int PFB_LDS_PER_CU = 160 * 1024; // gfx950
+// LDS of one workgroup
+constexpr size_t pfb_lds_bytes(uint32_t M) { return stream_bank_lds_bytes(M); }
+constexpr int PFB_LDS_PER_CU = STREAM_LDS_PER_CU;
 
-// workgroups a CU holds at a time: what its LDS fits, at most 8 (32 waves)
-constexpr int pfb_groups_per_cu(uint32_t M)
-{
-    return (size_t)PFB_LDS_PER_CU / pfb_lds_bytes(M) > 8 ? 8 : (int)((size_t)PFB_LDS_PER_CU / pfb_lds_bytes(M));
-}
+// workgroups a CU holds at a time
+constexpr int pfb_groups_per_cu(uint32_t M) { return stream_groups_per_cu(pfb_lds_bytes(M)); }
 
 } // namespace if_fir

@@ -139,10 +139,9 @@ __global__ __launch_bounds__(PSD_THREADS) void psd_carry_kernel(const void *__re
 template <int N, bool I16>
 static hipError_t launch_chunks(const PsdArgs &a)
 {
-    static DeviceSetup setup;
     int cus = 0;
     constexpr int lds = 2 * N * (int)sizeof(float2);
-    const hipError_t e = device_setup(setup, a.device, reinterpret_cast<const void *>(&psd_chunk_kernel<N, I16>), lds, &cus);
+    const hipError_t e = stream_kernel_setup<&psd_chunk_kernel<N, I16>>(a.device, lds, &cus);
     if (e != hipSuccess)
         return e;
     // a grid-stride loop over the chunks; the twiddles are staged once per workgroup, 160 KiB of LDS hold 160 / (16 N / 1024) of them

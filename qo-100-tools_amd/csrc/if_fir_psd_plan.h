@@ -12,11 +12,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define IF_FIR_PSD_HD __host__ __device__
-#else
-#define IF_FIR_PSD_HD
-#endif
+#include "if_fir_stream_plan.h"
 
 namespace if_fir
 {
@@ -28,13 +24,10 @@ constexpr int PSD_MAX_N = 4096;
 constexpr uint32_t PSD_MAX_SEGMENTS = 65535;
 constexpr uint64_t PSD_MAX_CALL_SEGMENTS = (uint64_t)1 << 31; // segments of one call: psd_chunk_entry counts them in 32 bits
 
-inline bool psd_size_ok(uint32_t N)
-{
-    return N == 256 || N == 512 || N == 1024 || N == 2048 || N == 4096;
-}
+inline bool psd_size_ok(uint32_t N) { return stream_size_ok(N, PSD_MIN_N); }
 
 // chunks of one frame
-IF_FIR_PSD_HD inline uint32_t psd_chunks_per_frame(uint32_t K)
+IF_FIR_STREAM_HD inline uint32_t psd_chunks_per_frame(uint32_t K)
 {
     return (K + PSD_CHUNK - 1) / PSD_CHUNK;
 }
@@ -85,7 +78,7 @@ inline bool psd_plan(uint64_t pos, uint64_t carried, uint64_t n, uint32_t N, uin
 // its segment count and the frame it belongs to counted from the call's first frame (the frame is for the plan checker: the
 // frame kernel finds its chunks itself).  32-bit: if_fir_psd_init refuses a context whose largest call could reach
 // PSD_MAX_CALL_SEGMENTS segments
-IF_FIR_PSD_HD inline void psd_chunk_entry(uint32_t chunk0, uint32_t c, uint32_t K, uint32_t *seg_rel, uint32_t *count, uint32_t *frame_rel)
+IF_FIR_STREAM_HD inline void psd_chunk_entry(uint32_t chunk0, uint32_t c, uint32_t K, uint32_t *seg_rel, uint32_t *count, uint32_t *frame_rel)
 {
     const uint32_t cpf = psd_chunks_per_frame(K);
     const uint32_t g = chunk0 + c, f = g / cpf, ci = g % cpf;
@@ -112,7 +105,7 @@ inline uint64_t psd_max_chunks(uint64_t n, uint32_t H, uint32_t K)
 
 // the in-place decimation-in-frequency transform of the chunk kernel runs radix-4 passes and, for N = 512 and 2048, one last
 // radix-2 pass; bin k ends at this position of the block (its digits reversed)
-IF_FIR_PSD_HD inline uint32_t psd_bin_position(uint32_t k, uint32_t N)
+IF_FIR_STREAM_HD inline uint32_t psd_bin_position(uint32_t k, uint32_t N)
 {
     uint32_t pos = 0, len = N;
     while (len > 1)

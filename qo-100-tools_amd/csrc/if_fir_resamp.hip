@@ -59,7 +59,7 @@ __global__ __launch_bounds__(RESAMP_THREADS) IF_FIR_SINGLE_READS void fir_resamp
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int hist_len = K - 1;
-    if (blockIdx.x == 0)
+    if (blockIdx.x == 0) // (its own loop: through a shared helper it compiles to other code, profiles/stream_plan_ab.txt)
         for (int i = tid; i < hist_len; i += RESAMP_THREADS)
         {
             const stream_v2f v = stream_load<I16>(in, hist, hist_len, N, N - hist_len + i);
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(RESAMP_THREADS) IF_FIR_SINGLE_READS void fir_resamp
         mine[k] = tid < W && i < tile_out;
         x0[k] = mine[k] ? (i / L) * M + dq : 0; // (idle places read the tile's first K samples and store nothing)
     }
-    const int top = K - ((K - 1) / RESAMP_SEG) * RESAMP_SEG; // taps of the highest segment, 1..16
+    const int top = stream_top_segment(K);
 
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x)
     {
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(RESAMP_THREADS) IF_FIR_SINGLE_READS void fir_resamp
             acc[k] = lost[k] = stream_v2f{0.f, 0.f};
         // e = K - 1 - j counts up from the oldest sample while j walks down through the segments
         int e = 0;
-        for (int len = top; e < K; len = RESAMP_SEG)
+        for (int len = top; e < K; len = STREAM_SEG)
         {
             stream_v2f seg[RESAMP_R];
 #pragma unroll
@@ -142,9 +142,8 @@ __global__ __launch_bounds__(RESAMP_THREADS) IF_FIR_SINGLE_READS void fir_resamp
 template <bool I16, bool CT>
 static hipError_t launch_t(const ResampArgs &a)
 {
-    static DeviceSetup setup;
     int cus = 0;
-    const hipError_t e = device_setup(setup, a.device, reinterpret_cast<const void *>(&fir_resamp_kernel<I16, CT>), RESAMP_LDS_MAX, &cus);
+    const hipError_t e = stream_kernel_setup<&fir_resamp_kernel<I16, CT>>(a.device, RESAMP_LDS_MAX, &cus);
     if (e != hipSuccess)
         return e;
     const ResampShape s = resamp_shape(a.T, a.L, a.M);

@@ -13,11 +13,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define IF_FIR_RESAMP_HD __host__ __device__
-#else
-#define IF_FIR_RESAMP_HD
-#endif
+#include "if_fir_stream_plan.h"
 
 namespace if_fir
 {
@@ -27,7 +23,6 @@ constexpr int RESAMP_MAX_M = 64;
 constexpr int RESAMP_MAX_TAPS = 4096;
 constexpr int RESAMP_THREADS = 256; // one workgroup
 constexpr int RESAMP_R = 4;         // outputs of one phase per lane
-constexpr int RESAMP_SEG = 16;      // phase taps per accumulation segment (SPEC §7)
 constexpr int RESAMP_X_MAX = 8192;  // input samples (float2) of one tile in LDS, overlap included
 
 // phase taps: every phase's row has K entries, zero where p + j L >= T
@@ -87,7 +82,7 @@ inline size_t resamp_lds_bytes(const ResampShape &s, int ctaps)
 constexpr int RESAMP_LDS_MAX = 8 * (RESAMP_MAX_TAPS + 2 * RESAMP_MAX_L) + 8 * RESAMP_X_MAX;
 
 // entry r of a call's period table
-IF_FIR_RESAMP_HD inline void resamp_period_entry(int t0, int r, int L, int M, int *p, int *dq)
+IF_FIR_STREAM_HD inline void resamp_period_entry(int t0, int r, int L, int M, int *p, int *dq)
 {
     const int v = t0 + r * M; // < 64 + 63 * 64
     *p = v % L;

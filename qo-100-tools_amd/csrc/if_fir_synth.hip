@@ -197,7 +197,7 @@ template <bool I16>
 __global__ __launch_bounds__(SYNTH_THREADS) void synth_carry_kernel(const void *__restrict__ in, const float2 *__restrict__ hist,
                                                                     float2 *__restrict__ hist_out, int64_t hist_len, int64_t n)
 {
-    // the last hist_len elements of (hist || call)
+    // the last hist_len elements of (hist || call) (its own loop: through a shared helper it compiles to other code, profiles/stream_plan_ab.txt)
     for (int64_t i = (int64_t)blockIdx.x * SYNTH_THREADS + threadIdx.x; i < hist_len; i += (int64_t)gridDim.x * SYNTH_THREADS)
     {
         const stream_v2f v = stream_load<I16>(in, hist, hist_len, n, n - hist_len + i);
@@ -208,19 +208,16 @@ __global__ __launch_bounds__(SYNTH_THREADS) void synth_carry_kernel(const void *
 template <int M, bool I16>
 static hipError_t launch_chunks(const SynthArgs &a)
 {
-    static DeviceSetup setup;
     int cus = 0;
     constexpr int lds = (int)synth_lds_bytes(M), B = (int)synth_batch(M);
-    const hipError_t e = device_setup(setup, a.device, reinterpret_cast<const void *>(&synth_transform_kernel<M, I16>), lds, &cus);
+    const hipError_t e = stream_kernel_setup<&synth_transform_kernel<M, I16>>(a.device, lds, &cus);
     if (e != hipSuccess)
         return e;
     const int64_t hist_len = (int64_t)(a.J - 1) * a.bins, n = a.frames * a.bins;
     if (a.route == SYNTH_ROUTE_LDS)
     {
-        static DeviceSetup ring_setup;
         const int ring_lds = (int)synth_lds_route_bytes(M, (uint32_t)a.J), NB = (a.J - 1 + B - 1) / B + 1;
-        const hipError_t re = device_setup(ring_setup, a.device, reinterpret_cast<const void *>(&synth_ring_kernel<M, I16>),
-                                           SYNTH_LDS_PER_CU / 2, nullptr);
+        const hipError_t re = stream_kernel_setup<&synth_ring_kernel<M, I16>>(a.device, SYNTH_LDS_PER_CU / 2, nullptr);
         if (re != hipSuccess)
             return re;
         const int64_t ring_batches = (a.frames + B - 1) / B;

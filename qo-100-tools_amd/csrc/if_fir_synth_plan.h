@@ -20,7 +20,7 @@ namespace if_fir
 constexpr int SYNTH_THREADS = 256;        // one workgroup
 constexpr int SYNTH_MAX_ROWS = 16;        // T <= 16 M
 constexpr int SYNTH_MAX_TERMS = 32;       // J = ceil(T / L)
-constexpr int SYNTH_BATCH_POINTS = 1024;  // a workgroup transforms at least this many points at a time: 1024 / M frames when M < 1024
+constexpr int SYNTH_BATCH_POINTS = STREAM_BANK_POINTS; // a workgroup transforms at least this many points at a time
 constexpr uint64_t SYNTH_MAX_CALL = (uint64_t)1 << 32;         // frames of one call
 constexpr uint64_t SYNTH_WORKSPACE_DEFAULT = (uint64_t)128 << 20; // bytes of transformed frames a chunk may hold (measured: DESIGN.md §3.19)
 constexpr uint64_t SYNTH_WORKSPACE_MAX = (uint64_t)1 << 30;      // (a chunk's outputs are counted in 32 bits)
@@ -32,10 +32,7 @@ enum
     SYNTH_ROUTE_LDS = 2,       // one kernel with a ring of transformed batches in LDS: where synth_lds_route_fits
 };
 
-inline bool synth_size_ok(uint32_t M)
-{
-    return M == 64 || M == 128 || M == 256 || M == 512 || M == 1024 || M == 2048 || M == 4096;
-}
+inline bool synth_size_ok(uint32_t M) { return stream_size_ok(M, 64); }
 
 // terms of an output's chain: J = ceil(T / L)
 inline uint32_t synth_terms(uint32_t T, uint32_t L)
@@ -50,24 +47,15 @@ inline bool synth_config_ok(uint32_t M, uint32_t T, uint32_t L)
            synth_terms(T, L) <= (uint32_t)SYNTH_MAX_TERMS;
 }
 
-// frames a workgroup transforms together (every lane of the 256 has a butterfly in every pass)
-constexpr uint32_t synth_batch(uint32_t M)
-{
-    return M >= (uint32_t)SYNTH_BATCH_POINTS ? 1u : (uint32_t)SYNTH_BATCH_POINTS / M;
-}
+// frames a workgroup transforms together
+constexpr uint32_t synth_batch(uint32_t M) { return stream_bank_batch(M); }
 
-// LDS of one workgroup of the transform kernel: the batch's points, the twiddles (float2 each) and the places (uint16)
-constexpr size_t synth_lds_bytes(uint32_t M)
-{
-    return (size_t)synth_batch(M) * M * 8 + (size_t)M * 8 + (size_t)M * 2;
-}
-constexpr int SYNTH_LDS_PER_CU = 160 * 1024; // gfx950
+// LDS of one workgroup of the transform kernel
+constexpr size_t synth_lds_bytes(uint32_t M) { return stream_bank_lds_bytes(M); }
+constexpr int SYNTH_LDS_PER_CU = STREAM_LDS_PER_CU;
 
-// workgroups a CU holds at a time: what its LDS fits, at most 8 (32 waves)
-constexpr int synth_groups_per_cu(uint32_t M)
-{
-    return (size_t)SYNTH_LDS_PER_CU / synth_lds_bytes(M) > 8 ? 8 : (int)((size_t)SYNTH_LDS_PER_CU / synth_lds_bytes(M));
-}
+// workgroups a CU holds at a time
+constexpr int synth_groups_per_cu(uint32_t M) { return stream_groups_per_cu(synth_lds_bytes(M)); }
 
 // LDS the one-kernel route would need: a ring of ceil((J-1)/B) + 1 transformed batches, the twiddles and the places; it fits
 // where two workgroups of it share a CU
@@ -81,11 +69,10 @@ inline bool synth_lds_route_fits(uint32_t M, uint32_t J)
     return 2 * synth_lds_route_bytes(M, J) <= (size_t)SYNTH_LDS_PER_CU;
 }
 
-// workgroups of the one-kernel route a CU holds at a time: what its LDS fits, at most 8
+// workgroups of the one-kernel route a CU holds at a time; 0 where not one fits (synth_route refuses the route there)
 inline int synth_lds_route_groups_per_cu(uint32_t M, uint32_t J)
 {
-    const size_t fit = (size_t)SYNTH_LDS_PER_CU / synth_lds_route_bytes(M, J);
-    return fit > 8 ? 8 : (int)fit;
+    return synth_lds_route_bytes(M, J) > (size_t)SYNTH_LDS_PER_CU ? 0 : stream_groups_per_cu(synth_lds_route_bytes(M, J));
 }
 
 // the plan prefers the LDS ring where at least four workgroups of it share a CU: measured, it wins there (M = 64 and 256 of the
@@ -193,7 +180,7 @@ inline uint32_t synth_slot_place(uint32_t s, uint32_t M)
 // input element of channel k in a frame of a span that starts at first_bin (-M/2 <= first_bin < M): element j holds channel
 // (first_bin + j) mod M, so j = (k - first_bin) mod M (M is a power of two); the span holds the channel when j < bins.  The
 // kernels call this
-IF_FIR_PSD_HD inline uint32_t synth_channel_index(int32_t first_bin, uint32_t k, uint32_t M)
+IF_FIR_STREAM_HD inline uint32_t synth_channel_index(int32_t first_bin, uint32_t k, uint32_t M)
 {
     return (uint32_t)((int32_t)k - first_bin) & (M - 1);
 }

@@ -558,7 +558,7 @@ class IfFir:
 
 class _StreamCtx:
     """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb and IfFirSynth share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
-    calls the three families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
+    calls the nine families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
     __init__, self._L, self._ctx and self._i16."""
     _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
 
