@@ -609,6 +609,53 @@ uint8_t if_fir_synth_process(if_fir_synth_t *pCtx, const void *pFramesIn, float 
 /* device pointers aligned to one element (input 8 bytes, 4 for int16; output 8 bytes), asynchronous on the context's stream */
 uint8_t if_fir_synth_process_device(if_fir_synth_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullFrames, uint64_t *pullSamples);
 
+/* ---- per-channel FIR stage over filter-bank frames (docs/SPEC.md §15; BUILD-DEFINED) -------------------------------------------
+ * The second stage of a two-stage channelizer in ONE pass: frames in the banks' layout in (in[a*ulBins + j], what if_fir_pfb_t
+ * emits and if_fir_synth_t takes), frames in the same layout out at 1/R of the frame rate, every bin filtered by its own real
+ * FIR row, decimated, and mixed by its own NCO.  Bin j is, by definition, the decimator of SPEC §2/§3.2 on the strided stream
+ * x_j[a] = in[a*B + j], a = absolute FRAME index since init/reset, x_j[a<0] = 0:
+ *     x'_j[a] = x_j[a] exp(-j 2 pi ((P_j a) mod 2^32) / 2^32),   y_j[n] = sum_{k<T} h_r[k] x'_j[n*R - k],   r = j or 0
+ *     out[n'*B + j] = y_j[n] for the n with c <= n*R < c + F, in order (c = frames before the call; possibly none)
+ * B = ulBins is any integer 1..4096 and is not tied to a bank's M.  Input complex64 or int16 pairs, output complex64.
+ * process(a||b) == process(a); process(b), bit for bit, wherever the frames are cut.
+ * Errors: 0 + if_fir_sub_last_error(); a failed call leaves the context usable and its position, history and NCO words unchanged.
+ * Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_sub if_fir_sub_t;
+
+typedef struct
+{
+    uint32_t ulBins;       /* B: elements per frame, 1..4096 */
+    uint32_t ulTaps;       /* T: taps per row, 1..128 */
+    uint32_t ulTapRows;    /* 1: one row for all bins; B: a row per bin */
+    uint32_t ulDecimation; /* R: input frames per output frame, 1..64 */
+} if_fir_sub_config_t;
+
+/* pfTaps: ulTapRows x ulTaps real float32 taps, row-major, used as given.  ullMaxFrames: 1..2^32, the most frames of one call
+ * (host or device pointers).  After init every NCO word is 0 */
+uint8_t if_fir_sub_init(if_fir_sub_t **ppCtx, const if_fir_sub_config_t *pCfg, const float *pfTaps, uint64_t ullMaxFrames, int32_t lDevice);
+void if_fir_sub_destroy(if_fir_sub_t *pCtx);
+/* zero the history and the stream position; the NCO words stay */
+uint8_t if_fir_sub_reset(if_fir_sub_t *pCtx);
+/* IF_FIR_INPUT_F32 or IF_FIR_INPUT_I16 (value = int16 * 2^-15); the history is float32, so a change keeps the stream */
+uint8_t if_fir_sub_set_input_format(if_fir_sub_t *pCtx, uint32_t ulFormat);
+/* pdFreq: B frequencies in cycles per INPUT FRAME, |f| <= 0.5, quantised to P_j = round(f_j 2^32) mod 2^32; NULL sets every word
+ * to 0.  The words of a call apply to every frame its outputs weigh, the carried history included (it holds unmixed frames): a
+ * retune is the phase step of if_fir_set_nco.  Setting the values in force changes nothing.  Waits for the context's stream */
+uint8_t if_fir_sub_set_nco(if_fir_sub_t *pCtx, const double *pdFreq);
+/* pdFreq receives the B quantised frequencies in force */
+uint8_t if_fir_sub_get_nco(const if_fir_sub_t *pCtx, double *pdFreq);
+uint8_t if_fir_sub_set_stream(if_fir_sub_t *pCtx, void *pStream);
+uint8_t if_fir_sub_synchronize(if_fir_sub_t *pCtx);
+const char *if_fir_sub_last_error(const if_fir_sub_t *pCtx);
+/* output frames a call with ullFrames frames would emit at the current stream position (0 when the call would be refused because
+ * the position would pass 2^64) */
+uint64_t if_fir_sub_frame_count(const if_fir_sub_t *pCtx, uint64_t ullFrames);
+/* host pointers, synchronous; ullFrames <= ullMaxFrames of init; pFramesIn holds ullFrames x ulBins elements, pfFramesOut
+ * if_fir_sub_frame_count() x ulBins complex64; *pullOutFrames (may be NULL) receives the frames emitted */
+uint8_t if_fir_sub_process(if_fir_sub_t *pCtx, const void *pFramesIn, float *pfFramesOut, uint64_t ullFrames, uint64_t *pullOutFrames);
+/* device pointers aligned to one element (input 8 bytes, 4 for int16; output 8 bytes), asynchronous on the context's stream */
+uint8_t if_fir_sub_process_device(if_fir_sub_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullFrames, uint64_t *pullOutFrames);
+
 #ifdef __cplusplus
 }
 #endif

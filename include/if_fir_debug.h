@@ -131,6 +131,10 @@ uint8_t if_fir_debug_synth_config(if_fir_synth_t *pCtx, uint32_t ulGridLimit, ui
 /* ullBytes > 0 replaces the workspace of transformed frames by one of that budget (at least ceil(T / L) frames, at most 2^30
  * bytes; the default is 128 MB); *pullFrames (may be NULL) receives the frames of a call one chunk then emits the outputs of */
 uint8_t if_fir_debug_synth_workspace(if_fir_synth_t *pCtx, uint64_t ullBytes, uint64_t *pullFrames);
+/* per-channel FIR stage (if_fir_sub_t): ulGridLimit as if_fir_debug_resamp_config, for both kernels of a call; *pulTileOutputs
+ * (may be NULL) receives the (output, bin) values one tile holds; an ullPosition other than UINT64_MAX sets the context's absolute
+ * FRAME index (the index of the next call's first frame) and zeroes its history */
+uint8_t if_fir_debug_sub_config(if_fir_sub_t *pCtx, uint32_t ulGridLimit, uint32_t *pulTileOutputs, uint64_t ullPosition);
 
 #ifdef __cplusplus
 }
