@@ -656,6 +656,55 @@ uint8_t if_fir_sub_process(if_fir_sub_t *pCtx, const void *pFramesIn, float *pfF
 /* device pointers aligned to one element (input 8 bytes, 4 for int16; output 8 bytes), asynchronous on the context's stream */
 uint8_t if_fir_sub_process_device(if_fir_sub_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullFrames, uint64_t *pullOutFrames);
 
+/* ---- per-bin interpolating FIR stage over frames, the transmit mirror of the stage above (docs/SPEC.md §16; BUILD-DEFINED) ------
+ * Frames in the banks' layout in (in[m*ulBins + j]), frames in the same layout out at R times the frame rate: every bin
+ * interpolated by R through its own real FIR row and mixed up by its own NCO, in ONE pass.  Bin j is, by definition, the
+ * interpolator of SPEC §6 with factor R and if_fir_interp_set_nco(f_j) on the strided stream x_j[m] = in[m*B + j], m = absolute
+ * INPUT frame index since init/reset, x_j[m<0] = 0; n = absolute OUTPUT frame index:
+ *     u_j[n] = x_j[n/R] if R divides n, else 0;   v_j[n] = sum_{k<T} h_r[k] u_j[n - k],   r = j or 0
+ *     y_j[n] = exp(+j 2 pi ((P_j n) mod 2^32) / 2^32) v_j[n];   out[(n - c*R)*B + j] = y_j[n] for c*R <= n < (c + F)*R
+ * (c = input frames before the call).  F frames in give exactly F*R frames out.  The taps are used as given (no gain of R).
+ * B = ulBins is any integer 1..4096 and is not tied to a bank's M.  Input complex64 or int16 pairs, output complex64.
+ * process(a||b) == process(a); process(b), bit for bit, wherever the frames are cut.
+ * Errors: 0 + if_fir_subup_last_error(); a failed call leaves the context usable and its position, history and NCO words unchanged.
+ * Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_subup if_fir_subup_t;
+
+typedef struct
+{
+    uint32_t ulBins;          /* B: elements per frame, 1..4096 */
+    uint32_t ulTaps;          /* T: taps per row, 1..2048, with ceil(T / R) <= 32 */
+    uint32_t ulTapRows;       /* 1: one row for all bins; B: a row per bin */
+    uint32_t ulInterpolation; /* R: output frames per input frame, 1..64 */
+} if_fir_subup_config_t;
+
+/* pfTaps: ulTapRows x ulTaps real float32 taps, row-major, used as given.  ullMaxFrames: 1..2^32, the most INPUT frames of one
+ * call (host or device pointers).  After init every NCO word is 0 */
+uint8_t if_fir_subup_init(if_fir_subup_t **ppCtx, const if_fir_subup_config_t *pCfg, const float *pfTaps, uint64_t ullMaxFrames, int32_t lDevice);
+void if_fir_subup_destroy(if_fir_subup_t *pCtx);
+/* zero the history and the stream position; the NCO words stay */
+uint8_t if_fir_subup_reset(if_fir_subup_t *pCtx);
+/* IF_FIR_INPUT_F32 or IF_FIR_INPUT_I16 (value = int16 * 2^-15); the history is float32, so a change keeps the stream */
+uint8_t if_fir_subup_set_input_format(if_fir_subup_t *pCtx, uint32_t ulFormat);
+/* pdFreq: B frequencies in cycles per OUTPUT FRAME, |f| <= 0.5, quantised to P_j = round(f_j 2^32) mod 2^32; NULL sets every
+ * word to 0.  The words in force at a call rotate that call's outputs by their absolute index (the history holds unmixed
+ * frames): a retune is the phase step of if_fir_interp_set_nco.  Setting the values in force changes nothing.  Waits for the
+ * context's stream */
+uint8_t if_fir_subup_set_nco(if_fir_subup_t *pCtx, const double *pdFreq);
+/* pdFreq receives the B quantised frequencies in force */
+uint8_t if_fir_subup_get_nco(const if_fir_subup_t *pCtx, double *pdFreq);
+uint8_t if_fir_subup_set_stream(if_fir_subup_t *pCtx, void *pStream);
+uint8_t if_fir_subup_synchronize(if_fir_subup_t *pCtx);
+const char *if_fir_subup_last_error(const if_fir_subup_t *pCtx);
+/* output frames a call with ullFrames frames would emit: ullFrames * R (0 when the call would be refused because its last
+ * output index would pass 2^64 - 1) */
+uint64_t if_fir_subup_frame_count(const if_fir_subup_t *pCtx, uint64_t ullFrames);
+/* host pointers, synchronous; ullFrames <= ullMaxFrames of init; pFramesIn holds ullFrames x ulBins elements, pfFramesOut
+ * if_fir_subup_frame_count() x ulBins complex64; *pullOutFrames (may be NULL) receives the frames emitted */
+uint8_t if_fir_subup_process(if_fir_subup_t *pCtx, const void *pFramesIn, float *pfFramesOut, uint64_t ullFrames, uint64_t *pullOutFrames);
+/* device pointers aligned to one element (input 8 bytes, 4 for int16; output 8 bytes), asynchronous on the context's stream */
+uint8_t if_fir_subup_process_device(if_fir_subup_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullFrames, uint64_t *pullOutFrames);
+
 #ifdef __cplusplus
 }
 #endif

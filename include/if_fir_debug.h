@@ -135,6 +135,10 @@ uint8_t if_fir_debug_synth_workspace(if_fir_synth_t *pCtx, uint64_t ullBytes, ui
  * (may be NULL) receives the (output, bin) values one tile holds; an ullPosition other than UINT64_MAX sets the context's absolute
  * FRAME index (the index of the next call's first frame) and zeroes its history */
 uint8_t if_fir_debug_sub_config(if_fir_sub_t *pCtx, uint32_t ulGridLimit, uint32_t *pulTileOutputs, uint64_t ullPosition);
+/* per-bin interpolating FIR stage (if_fir_subup_t): ulGridLimit as if_fir_debug_resamp_config, for both kernels of a call;
+ * *pulTileOutputs (may be NULL) receives the (output, bin) values one tile holds; an ullPosition other than UINT64_MAX sets the
+ * context's absolute INPUT FRAME index (the index of the next call's first frame) and zeroes its history */
+uint8_t if_fir_debug_subup_config(if_fir_subup_t *pCtx, uint32_t ulGridLimit, uint32_t *pulTileOutputs, uint64_t ullPosition);
 
 #ifdef __cplusplus
 }

@@ -60,6 +60,9 @@ EXPORTS = [
     "if_fir_sub_init", "if_fir_sub_destroy", "if_fir_sub_reset", "if_fir_sub_set_input_format", "if_fir_sub_set_nco", "if_fir_sub_get_nco",
     "if_fir_sub_set_stream", "if_fir_sub_synchronize", "if_fir_sub_last_error", "if_fir_sub_frame_count", "if_fir_sub_process",
     "if_fir_sub_process_device",
+    "if_fir_subup_init", "if_fir_subup_destroy", "if_fir_subup_reset", "if_fir_subup_set_input_format", "if_fir_subup_set_nco",
+    "if_fir_subup_get_nco", "if_fir_subup_set_stream", "if_fir_subup_synchronize", "if_fir_subup_last_error", "if_fir_subup_frame_count",
+    "if_fir_subup_process", "if_fir_subup_process_device",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
@@ -70,7 +73,7 @@ DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_ta
                "if_fir_debug_combiner_config", "if_fir_debug_combiner_seek", "if_fir_debug_combiner_tables",
                "if_fir_debug_ddc_config", "if_fir_debug_duc_config", "if_fir_debug_arb_config",
                "if_fir_debug_pfb_config", "if_fir_debug_synth_config", "if_fir_debug_synth_workspace",
-               "if_fir_debug_sub_config"]
+               "if_fir_debug_sub_config", "if_fir_debug_subup_config"]
 MC_ID_BYTES = 128
 
 
@@ -93,6 +96,11 @@ class SynthConfig(ctypes.Structure):
 class SubConfig(ctypes.Structure):
     """if_fir_sub_config_t"""
     _fields_ = [("ulBins", ctypes.c_uint32), ("ulTaps", ctypes.c_uint32), ("ulTapRows", ctypes.c_uint32), ("ulDecimation", ctypes.c_uint32)]
+
+
+class SubUpConfig(ctypes.Structure):
+    """if_fir_subup_config_t"""
+    _fields_ = [("ulBins", ctypes.c_uint32), ("ulTaps", ctypes.c_uint32), ("ulTapRows", ctypes.c_uint32), ("ulInterpolation", ctypes.c_uint32)]
 
 
 class IfFirError(RuntimeError):
@@ -206,7 +214,7 @@ def _load(path, dev):
     L.if_fir_mc_get_chunk_samples.restype = u8
     # the streaming contexts (_StreamCtx): what the families declare alike, then what each has of its own
     for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_", "if_fir_ddc_", "if_fir_duc_", "if_fir_arb_",
-                   "if_fir_pfb_", "if_fir_synth_", "if_fir_sub_"):
+                   "if_fir_pfb_", "if_fir_synth_", "if_fir_sub_", "if_fir_subup_"):
         for name, args, res in (("destroy", [vp], None), ("reset", [vp], u8), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
                                 ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p)):
             getattr(L, prefix + name).argtypes = args
@@ -302,6 +310,21 @@ def _load(path, dev):
     if dev:
         L.if_fir_debug_sub_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
         L.if_fir_debug_sub_config.restype = u8
+    L.if_fir_subup_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(SubUpConfig), f32p, u64, i32]
+    L.if_fir_subup_init.restype = u8
+    L.if_fir_subup_set_nco.argtypes = [vp, f64p]
+    L.if_fir_subup_set_nco.restype = u8
+    L.if_fir_subup_get_nco.argtypes = [vp, f64p]
+    L.if_fir_subup_get_nco.restype = u8
+    L.if_fir_subup_frame_count.argtypes = [vp, u64]
+    L.if_fir_subup_frame_count.restype = u64
+    L.if_fir_subup_process.argtypes = [vp, vp, f32p, u64, ctypes.POINTER(u64)]
+    L.if_fir_subup_process.restype = u8
+    L.if_fir_subup_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.if_fir_subup_process_device.restype = u8
+    if dev:
+        L.if_fir_debug_subup_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
+        L.if_fir_debug_subup_config.restype = u8
         L.if_fir_debug_synth_config.argtypes = [vp, u32, u32, ctypes.POINTER(u32), u64]
         L.if_fir_debug_synth_config.restype = u8
         L.if_fir_debug_synth_workspace.argtypes = [vp, u64, ctypes.POINTER(u64)]
@@ -580,8 +603,8 @@ class IfFir:
 
 
 class _StreamCtx:
-    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb, IfFirSynth and IfFirSub share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
-    calls the ten families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
+    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb, IfFirSynth, IfFirSub and IfFirSubUp share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
+    calls the eleven families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
     __init__, self._L, self._ctx and self._i16."""
     _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
 
@@ -1355,6 +1378,86 @@ class IfFirSub(_StreamCtx):
         tile = ctypes.c_uint32(0)
         self._check(self._L.if_fir_debug_sub_config(self._ctx, int(grid_limit), ctypes.byref(tile),
                                                     self.NO_POSITION if position is None else int(position)))
+        return int(tile.value)
+
+
+class IfFirSubUp(_StreamCtx):
+    """One if_fir_subup_t: the transmit mirror of IfFirSub over frames of `bins` elements (what IfFirSynth.process takes): every
+    bin interpolated by `interpolation` through its own row of `taps` (one row for all bins, or a (bins, T) array) and mixed up
+    by its own NCO in one pass (docs/SPEC.md §16).  Methods mirror the C entry points; F frames in give F * interpolation out."""
+    _PREFIX = "if_fir_subup_"
+    NO_POSITION = (1 << 64) - 1
+
+    def __init__(self, taps, bins, interpolation=1, max_frames=1 << 12, device=0, dev=False, tap_rows=None):
+        self._L = dev_lib() if dev else lib()
+        self._ctx = ctypes.c_void_p()
+        self._dev = bool(dev)
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        self.bins = int(bins)
+        self.interpolation = int(interpolation)
+        self.tap_rows = int(tap_rows) if tap_rows is not None else (taps.shape[0] if taps.ndim == 2 else 1)
+        self.taps = taps.reshape(-1)
+        self.ntaps = self.taps.size // self.tap_rows if self.tap_rows > 0 else 0
+        self._i16 = False
+        if not all(0 <= v < 1 << 32 for v in (self.bins, self.ntaps, self.tap_rows, self.interpolation)):
+            raise IfFirError("if_fir_subup_init: bins, taps, tap rows and interpolation must be unsigned 32-bit integers")
+        cfg = SubUpConfig(self.bins, self.ntaps, self.tap_rows, self.interpolation)
+        if not self._L.if_fir_subup_init(ctypes.byref(self._ctx), ctypes.byref(cfg), _f32p(self.taps) if self.taps.size else None,
+                                         int(max_frames), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._c("last_error")(None).decode())
+
+    def set_nco(self, freqs):
+        """if_fir_subup_set_nco(): `bins` frequencies in cycles per OUTPUT frame, |f| <= 0.5; None sets every word to 0."""
+        if freqs is None:
+            self._check(self._L.if_fir_subup_set_nco(self._ctx, None))
+            return
+        f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        if f.size != self.bins:
+            raise IfFirError("if_fir_subup_set_nco: %d frequencies for %d bins" % (f.size, self.bins))
+        self._check(self._L.if_fir_subup_set_nco(self._ctx, f.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+
+    def get_nco(self):
+        """if_fir_subup_get_nco(): the quantised frequencies in force, one per bin."""
+        f = np.zeros(self.bins, dtype=np.float64)
+        self._check(self._L.if_fir_subup_get_nco(self._ctx, f.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return f
+
+    def frame_count(self, frames):
+        """if_fir_subup_frame_count(): output frames of a call with `frames` frames (0 where the call would be refused)."""
+        return int(self._L.if_fir_subup_frame_count(self._ctx, int(frames)))
+
+    def process(self, frames):
+        """if_fir_subup_process(): a host (frames, bins) array in (complex64 / interleaved float32, or int16 pairs after
+        set_input_format(INPUT_I16)); returns the (frames * interpolation, bins) complex64 array."""
+        x, n = self._host_input(frames)
+        if n % self.bins:
+            raise IfFirError("if_fir_subup_process: %d elements are not whole frames of %d bins" % (n, self.bins))
+        f = n // self.bins
+        out = np.empty((self.frame_count(f), self.bins), dtype=np.complex64)
+        m = ctypes.c_uint64(0)
+        dummy = np.zeros(2, dtype=np.float32)
+        self._check(self._L.if_fir_subup_process(self._ctx, ctypes.c_void_p(x.ctypes.data if f else dummy.ctypes.data),
+                                                 _f32p(out.view(np.float32) if out.size else dummy), f, ctypes.byref(m)))
+        assert m.value == out.shape[0]
+        return out
+
+    def process_device(self, dev_in, dev_out, frames):
+        """if_fir_subup_process_device(): raw device pointers (ints), asynchronous.  Returns the frames emitted."""
+        m = ctypes.c_uint64(0)
+        self._check(self._L.if_fir_subup_process_device(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
+                                                        int(frames), ctypes.byref(m)))
+        return int(m.value)
+
+    def debug_config(self, grid_limit=0, position=None):
+        """if_fir_debug_subup_config() (development library: construct with dev=True): at most grid_limit workgroups per
+        kernel (0 = the launcher's choice); position (optional) = the absolute index of the next call's first INPUT frame, with
+        the history zeroed.  Returns the (output, bin) values one tile holds."""
+        if not self._dev:
+            raise IfFirError("if_fir_debug_subup_config is in the development library only: construct with dev=True")
+        tile = ctypes.c_uint32(0)
+        self._check(self._L.if_fir_debug_subup_config(self._ctx, int(grid_limit), ctypes.byref(tile),
+                                                      self.NO_POSITION if position is None else int(position)))
         return int(tile.value)
 
 
