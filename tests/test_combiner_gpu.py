@@ -54,7 +54,8 @@ def test_combiner_matches_float64_reference(gpu_ok, fir, oracle, route, L, C, T,
 
 
 STREAM_SHAPES = [("fft", 8, 8, 255, False), ("fft", 64, 3, 31, True), ("fft", 4, 2, 3073, False), ("fft", 16, 16, 1023, True),
-                 ("generic", 3, 2, 255, True), ("generic", 16, 3, 1023, False)]
+                 ("generic", 3, 2, 255, True), ("generic", 16, 3, 1023, False),
+                 ("fft", 32, 3, 513, True), ("fft", 8, 2, 2049, False)]   # rows 8 and 32 (and L = 32)
 
 
 @pytest.mark.gpu

@@ -1,6 +1,7 @@
 """The channel combiner's host side (no GPU): its C ABI in the header and the libraries, the float64 reference against the
 third-party form, the identity the overlap-save route rests on, the host-built multiply tables, a complex64 model of the route
-against SPEC §3's bound, the tap-boundary sensitivity of the test matrix, and the compiled kernels' resources."""
+against SPEC §3's bound, the tap-boundary sensitivity of the test matrices, the faults of the route that the boundary and
+bin-move cases notice, and the compiled kernels' resources."""
 import os
 import re
 import subprocess
@@ -21,6 +22,9 @@ COMBINER_ABI = {"if_fir_combiner_init", "if_fir_combiner_init_complex", "if_fir_
 COMBINER_DEV = {"if_fir_debug_combiner_config", "if_fir_debug_combiner_seek", "if_fir_debug_combiner_tables"}
 TOL = 1e-6   # docs/SPEC.md §3
 ALL_CASES = cr.cases("fft") + cr.cases("generic")
+# the cases of tests/test_combiner_matrix_gpu.py: the boundary matrix (less what the matrix above has already) and the bin moves
+BOUNDARY_NEW = [c for c in cr.boundary_cases() if c not in ALL_CASES]
+MOVES = [pytest.param(*c, id=cr.case_id(c)) for c in cr.move_cases()]
 
 
 def _defined(path):
@@ -100,14 +104,18 @@ def test_host_multiply_tables(fir, complex_taps, centre):
         fir.debug_combiner_tables(t, 0.6, complex_taps)
 
 
-@pytest.mark.parametrize("L,C,T,ct,i16", cr.cases("fft"))
+def _first_out(L, C):
+    return C.seek * L if isinstance(C, cr.Words) else 0
+
+
+@pytest.mark.parametrize("L,C,T,ct,i16", cr.cases("fft") + BOUNDARY_NEW + MOVES)
 def test_complex64_model_stays_under_half_the_bound(fir, L, C, T, ct, i16):
     """a plain single-precision implementation of the route (tests/combiner_ref.py, model_c64) misses the float64 reference by
-    less than half of SPEC §3's bound on every overlap-save case of the GPU matrix"""
+    less than half of SPEC §3's bound on every overlap-save case of the GPU matrix, of the boundary matrix and of the bin moves"""
     assert hasattr(fir, "IfFirCombiner")
     taps, _, xs, _, words, ref = cr.case_reference(L, C, T, ct, i16)
-    l2, mx = rel(cr.model_c64(taps, xs, L, words, ct), ref)
-    print("combiner-model L=%d C=%d T=%d ct=%d i16=%d l2=%.3g max=%.3g" % (L, C, T, ct, i16, l2, mx))
+    l2, mx = rel(cr.model_c64(taps, xs, L, words, ct, first_out=_first_out(L, C)), ref)
+    print("combiner-model L=%d C=%s T=%d ct=%d i16=%d l2=%.3g max=%.3g" % (L, C, T, ct, i16, l2, mx))
     assert l2 <= 0.5 * TOL and mx <= 0.5 * TOL, (l2, mx)
 
 
@@ -151,14 +159,51 @@ def _edge_moves(L, C, T, ct, i16, taps=None):
     return moves
 
 
-@pytest.mark.parametrize("L,C,T,ct,i16", ALL_CASES)
+@pytest.mark.parametrize("L,C,T,ct,i16", ALL_CASES + BOUNDARY_NEW + MOVES)
 def test_edge_taps_of_every_channel_move_the_reference(fir, L, C, T, ct, i16):
     """matrix_util.edge_taps: h[0] or h[T-1] missing from ONE channel's filter moves the reference by about 1 / sqrt(T C), more
     than 1e-4 = 100 x the tolerance, for every channel of every matrix shape: a boundary off by one in any channel fails the
     GPU comparison"""
     assert hasattr(fir, "IfFirCombiner")
     moves = _edge_moves(L, C, T, ct, i16)
-    assert len(moves) == (2 if T > 1 else 1) * C and min(moves) > 1e-4, min(moves)
+    channels = len(C) if isinstance(C, cr.Words) else C
+    assert len(moves) == (2 if T > 1 else 1) * channels and min(moves) > 1e-4, min(moves)
+
+
+def _model_error(case, **fault):
+    L, C, T, ct, i16 = case
+    taps, _, xs, _, words, ref = cr.case_reference(L, C, T, ct, i16)
+    return rel(cr.model_c64(taps, xs, L, words, ct, first_out=_first_out(L, C), **fault), ref)
+
+
+def test_new_cases_notice_the_faults_they_are_for(fir):
+    """model_c64's test-only switches, each one fault of the route's index algebra, push the model more than 100 x the
+    tolerance (on both norms) from the float64 reference on the cases of tests/test_combiner_matrix_gpu.py aimed at it:
+      - the bins moved by G + 1: every bin-move case, the words alone included;
+      - a block kept from one input sample before the overlap (overlap - L): every boundary case whose filter fills its overlap
+        (T - 1 = 64 rows), where h[T-1] then wraps onto the block's last sample;
+      - one channel multiplied by the table of its neighbour's residual (channel 6, r = 2^19 - 1, with channel 5's r = -2^19):
+        every case that carries all the words.
+    A block kept from overlap - 1 is no fault and is held to the bound instead: the block's first point is a multiple of 64, so
+    the one value h[T-1] reaches across the overlap is a zero between two input samples (L >= 4)."""
+    assert hasattr(fir, "IfFirCombiner")
+    far = 100 * TOL
+    moves = cr.move_cases()
+    assert len(moves) == 10 + 2 * len(cr.MOVE_WORDS)
+    for case in moves:
+        l2, mx = _model_error(case, move_extra=1)
+        assert l2 > far and mx > far, (case, l2, mx)
+        if len(case[1]) > 1:
+            assert cr.split_word(case[1][6])[1] == (1 << 19) - 1 and cr.split_word(case[1][5])[1] == -(1 << 19)
+            l2, mx = _model_error(case, table_of=(6, 5))
+            assert l2 > far and mx > far, (case, l2, mx)
+    full = [c for c in cr.boundary_cases() if c[2] - 1 == 64 * cr.overlap_rows(c[2])]
+    assert len(full) == 5 * len(cr.BOUNDARY_L) and {cr.overlap_rows(c[2]) for c in full} == {4, 8, 16, 32, 48}
+    for case in full:
+        l2, mx = _model_error(case, keep_early=case[0])
+        assert l2 > far and mx > far, (case, l2, mx)
+        l2, mx = _model_error(case, keep_early=1)
+        assert l2 <= 0.5 * TOL and mx <= 0.5 * TOL, (case, l2, mx)
 
 
 def test_edge_tap_check_fails_on_a_windowed_design(fir):
