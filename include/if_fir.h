@@ -705,6 +705,49 @@ uint8_t if_fir_subup_process(if_fir_subup_t *pCtx, const void *pFramesIn, float 
 /* device pointers aligned to one element (input 8 bytes, 4 for int16; output 8 bytes), asynchronous on the context's stream */
 uint8_t if_fir_subup_process_device(if_fir_subup_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullFrames, uint64_t *pullOutFrames);
 
+/* ---- real-input polyphase filter bank (docs/SPEC.md §17; BUILD-DEFINED) --------------------------------------------------------
+ * The M/2 + 1 distinct channels of a uniform grid out of one REAL sample stream in ONE pass, M = 128 .. 8192: the bank of
+ * if_fir_pfb_t fed (r, 0), without widening the stream, folding zeros or transforming M points.  Channel k is the down-converter
+ * of SPEC §10 (if_fir_ddc_t) with phase word k * 2^32 / M, the real prototype h[0..T-1] (T <= 16 M) and decimation D = ulHop
+ * (1 <= D <= M, any integer):
+ *     y_k[m] = sum_{t<T} h[t] r[a-t] exp(-j 2 pi k (a-t) / M),   a = m*D = absolute index since init/reset,   r[i<0] = 0,   k = 0 .. M/2
+ * The channels above M/2 are the complex conjugates y_{M-k} = conj y_k and are not offered; channels 0 and M/2 are real (their
+ * imaginary part is exactly zero).  Input is one float32 or one int16 (value = int16 * 2^-15) per sample.  Output is complex64
+ * (float32 I, Q), frame-major, the layout of if_fir_pfb_t: out[m*ulBins + j] = channel ulFirstBin + j of frame m.  A call whose
+ * first sample has absolute index c and which brings N samples emits the frames with m*D in [c, c+N) (possibly none).
+ * process(a||b) == process(a); process(b), bit for bit, wherever the stream is cut.
+ * Errors: 0 + if_fir_rpfb_last_error(); a failed call leaves the context usable and its stream position unchanged.
+ * Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_rpfb if_fir_rpfb_t;
+
+typedef struct
+{
+    uint32_t ulChannels; /* M: 128, 256, 512, 1024, 2048, 4096 or 8192 */
+    uint32_t ulHop;      /* D: input samples per frame, 1..M */
+    uint32_t ulFirstBin; /* first output channel, 0 <= ulFirstBin */
+    uint32_t ulBins;     /* output channels per frame, >= 1; ulFirstBin + ulBins <= M/2 + 1: the span does not wrap */
+} if_fir_rpfb_config_t;
+
+/* pfTaps: ulTaps real float32 taps, 1 <= ulTaps <= 16 M, used as given.  ullMaxSamples: 1..2^40, the most samples of one call */
+uint8_t if_fir_rpfb_init(if_fir_rpfb_t **ppCtx, const if_fir_rpfb_config_t *pCfg, const float *pfTaps, uint32_t ulTaps,
+                         uint64_t ullMaxSamples, int32_t lDevice);
+void if_fir_rpfb_destroy(if_fir_rpfb_t *pCtx);
+/* zero the history and the stream position */
+uint8_t if_fir_rpfb_reset(if_fir_rpfb_t *pCtx);
+/* IF_FIR_INPUT_F32 or IF_FIR_INPUT_I16 (value = int16 * 2^-15); the history is float32, so a change keeps the stream */
+uint8_t if_fir_rpfb_set_input_format(if_fir_rpfb_t *pCtx, uint32_t ulFormat);
+uint8_t if_fir_rpfb_set_stream(if_fir_rpfb_t *pCtx, void *pStream);
+uint8_t if_fir_rpfb_synchronize(if_fir_rpfb_t *pCtx);
+const char *if_fir_rpfb_last_error(const if_fir_rpfb_t *pCtx);
+/* frames a call with ullSamples samples would emit at the current stream position */
+uint64_t if_fir_rpfb_frame_count(const if_fir_rpfb_t *pCtx, uint64_t ullSamples);
+/* host pointers, synchronous; ullSamples <= ullMaxSamples of init; pIn holds ullSamples real samples, pfIQOut
+ * if_fir_rpfb_frame_count() x ulBins complex64; *pullFrames (may be NULL) receives the frames emitted */
+uint8_t if_fir_rpfb_process(if_fir_rpfb_t *pCtx, const void *pIn, float *pfIQOut, uint64_t ullSamples, uint64_t *pullFrames);
+/* device pointers aligned to one sample (input 4 bytes, 2 for int16; output 8 bytes), asynchronous on the context's stream;
+ * pDevOut holds if_fir_rpfb_frame_count() x ulBins samples */
+uint8_t if_fir_rpfb_process_device(if_fir_rpfb_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples, uint64_t *pullFrames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,8 @@ uint8_t if_fir_debug_sub_config(if_fir_sub_t *pCtx, uint32_t ulGridLimit, uint32
  * *pulTileOutputs (may be NULL) receives the (output, bin) values one tile holds; an ullPosition other than UINT64_MAX sets the
  * context's absolute INPUT FRAME index (the index of the next call's first frame) and zeroes its history */
 uint8_t if_fir_debug_subup_config(if_fir_subup_t *pCtx, uint32_t ulGridLimit, uint32_t *pulTileOutputs, uint64_t ullPosition);
+/* real-input polyphase filter bank (if_fir_rpfb_t): the three arguments as if_fir_debug_pfb_config */
+uint8_t if_fir_debug_rpfb_config(if_fir_rpfb_t *pCtx, uint32_t ulGridLimit, uint32_t *pulGroupFrames, uint64_t ullPosition);
 
 #ifdef __cplusplus
 }

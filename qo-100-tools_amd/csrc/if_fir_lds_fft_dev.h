@@ -1,5 +1,5 @@
 // if_fir_lds_fft_dev.h — the in-place LDS transform the power-spectrum estimator (if_fir_psd.hip), the polyphase filter bank
-// (if_fir_pfb.hip) and the polyphase synthesis bank (if_fir_synth.hip) share, under the rule of if_fir_stream_dev.h: nothing here branches on which family includes it.
+// (if_fir_pfb.hip), the polyphase synthesis bank (if_fir_synth.hip) and the real-input bank (if_fir_rpfb.hip, at M/2 points) share, under the rule of if_fir_stream_dev.h: nothing here branches on which family includes it.
 //
 // TOTAL complex points in LDS hold TOTAL / N independent blocks of N points each, block b at [b N, b N + N).  Every block gets the
 // same forward decimation-in-frequency transform: radix-4 passes that meet at workgroup barriers and, when N is an odd power of

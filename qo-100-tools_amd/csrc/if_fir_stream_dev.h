@@ -88,6 +88,30 @@ __device__ __forceinline__ float stream_load_real(const void *__restrict__ in, c
     return v;
 }
 
+// the REAL samples j and j + 1 in one load where both lie in the call (8 bytes at a 4-byte boundary, or 4 at a 2-byte one: the
+// sample's own alignment is all that holds, j has either parity); at the call's edges two bounds-checked loads
+template <bool I16>
+__device__ __forceinline__ stream_v2f stream_load_real2(const void *__restrict__ in, const float *__restrict__ hist, int64_t hist_len,
+                                                        int64_t N, int64_t j)
+{
+    if (j >= 0 && j + 1 < N)
+    {
+        if constexpr (I16)
+        {
+            short s[2];
+            __builtin_memcpy(s, static_cast<const short *>(in) + j, sizeof s);
+            return stream_v2f{(float)s[0] * (1.0f / 32768.0f), (float)s[1] * (1.0f / 32768.0f)};
+        }
+        else
+        {
+            stream_v2f v;
+            __builtin_memcpy(&v, static_cast<const float *>(in) + j, sizeof v);
+            return v;
+        }
+    }
+    return stream_v2f{stream_load_real<I16>(in, hist, hist_len, N, j), stream_load_real<I16>(in, hist, hist_len, N, j + 1)};
+}
+
 // compensated (two-sum) addition: acc += x, what the rounding of that add lost onto `lost` (float or a vector of floats)
 template <class V>
 __device__ __forceinline__ void two_sum_add(V &acc, V &lost, const V &x)

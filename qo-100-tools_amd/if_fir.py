@@ -63,6 +63,8 @@ EXPORTS = [
     "if_fir_subup_init", "if_fir_subup_destroy", "if_fir_subup_reset", "if_fir_subup_set_input_format", "if_fir_subup_set_nco",
     "if_fir_subup_get_nco", "if_fir_subup_set_stream", "if_fir_subup_synchronize", "if_fir_subup_last_error", "if_fir_subup_frame_count",
     "if_fir_subup_process", "if_fir_subup_process_device",
+    "if_fir_rpfb_init", "if_fir_rpfb_destroy", "if_fir_rpfb_reset", "if_fir_rpfb_set_input_format", "if_fir_rpfb_set_stream",
+    "if_fir_rpfb_synchronize", "if_fir_rpfb_last_error", "if_fir_rpfb_frame_count", "if_fir_rpfb_process", "if_fir_rpfb_process_device",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
@@ -73,7 +75,7 @@ DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_ta
                "if_fir_debug_combiner_config", "if_fir_debug_combiner_seek", "if_fir_debug_combiner_tables",
                "if_fir_debug_ddc_config", "if_fir_debug_duc_config", "if_fir_debug_arb_config",
                "if_fir_debug_pfb_config", "if_fir_debug_synth_config", "if_fir_debug_synth_workspace",
-               "if_fir_debug_sub_config", "if_fir_debug_subup_config"]
+               "if_fir_debug_sub_config", "if_fir_debug_subup_config", "if_fir_debug_rpfb_config"]
 MC_ID_BYTES = 128
 
 
@@ -86,6 +88,11 @@ class PsdConfig(ctypes.Structure):
 class PfbConfig(ctypes.Structure):
     """if_fir_pfb_config_t"""
     _fields_ = [("ulChannels", ctypes.c_uint32), ("ulHop", ctypes.c_uint32), ("lFirstBin", ctypes.c_int32), ("ulBins", ctypes.c_uint32)]
+
+
+class RpfbConfig(ctypes.Structure):
+    """if_fir_rpfb_config_t"""
+    _fields_ = [("ulChannels", ctypes.c_uint32), ("ulHop", ctypes.c_uint32), ("ulFirstBin", ctypes.c_uint32), ("ulBins", ctypes.c_uint32)]
 
 
 class SynthConfig(ctypes.Structure):
@@ -214,7 +221,7 @@ def _load(path, dev):
     L.if_fir_mc_get_chunk_samples.restype = u8
     # the streaming contexts (_StreamCtx): what the families declare alike, then what each has of its own
     for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_", "if_fir_ddc_", "if_fir_duc_", "if_fir_arb_",
-                   "if_fir_pfb_", "if_fir_synth_", "if_fir_sub_", "if_fir_subup_"):
+                   "if_fir_pfb_", "if_fir_synth_", "if_fir_sub_", "if_fir_subup_", "if_fir_rpfb_"):
         for name, args, res in (("destroy", [vp], None), ("reset", [vp], u8), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
                                 ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p)):
             getattr(L, prefix + name).argtypes = args
@@ -322,7 +329,17 @@ def _load(path, dev):
     L.if_fir_subup_process.restype = u8
     L.if_fir_subup_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.if_fir_subup_process_device.restype = u8
+    L.if_fir_rpfb_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(RpfbConfig), f32p, u32, u64, i32]
+    L.if_fir_rpfb_init.restype = u8
+    L.if_fir_rpfb_frame_count.argtypes = [vp, u64]
+    L.if_fir_rpfb_frame_count.restype = u64
+    L.if_fir_rpfb_process.argtypes = [vp, vp, f32p, u64, ctypes.POINTER(u64)]
+    L.if_fir_rpfb_process.restype = u8
+    L.if_fir_rpfb_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.if_fir_rpfb_process_device.restype = u8
     if dev:
+        L.if_fir_debug_rpfb_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
+        L.if_fir_debug_rpfb_config.restype = u8
         L.if_fir_debug_subup_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
         L.if_fir_debug_subup_config.restype = u8
         L.if_fir_debug_synth_config.argtypes = [vp, u32, u32, ctypes.POINTER(u32), u64]
@@ -603,8 +620,8 @@ class IfFir:
 
 
 class _StreamCtx:
-    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb, IfFirSynth, IfFirSub and IfFirSubUp share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
-    calls the eleven families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
+    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb, IfFirSynth, IfFirSub, IfFirSubUp and IfFirRpfb share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
+    calls the twelve families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
     __init__, self._L, self._ctx and self._i16."""
     _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
 
@@ -1216,6 +1233,74 @@ class IfFirPfb(_StreamCtx):
         group = ctypes.c_uint32(0)
         self._check(self._L.if_fir_debug_pfb_config(self._ctx, int(grid_limit), ctypes.byref(group),
                                                     self.NO_POSITION if position is None else int(position)))
+        self._grid_limit = int(grid_limit)
+        return int(group.value)
+
+
+class IfFirRpfb(_StreamCtx):
+    """One if_fir_rpfb_t: the `channels` / 2 + 1 distinct channels of a uniform grid out of one REAL sample stream in one pass, a
+    frame of `bins` complex64 values every `hop` input samples (docs/SPEC.md §17).  Methods mirror the C entry points; how many
+    frames a call emits depends on the stream position (frame_count)."""
+    _PREFIX = "if_fir_rpfb_"
+    NO_POSITION = (1 << 64) - 1
+
+    def __init__(self, taps, channels, hop=None, first_bin=0, bins=None, max_samples=1 << 20, device=0, dev=False):
+        self._L = dev_lib() if dev else lib()
+        self._ctx = ctypes.c_void_p()
+        self._dev, self._grid_limit = bool(dev), 0
+        taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        self.taps = taps
+        self.channels = int(channels)
+        self.hop = self.channels if hop is None else int(hop)
+        self.first_bin = int(first_bin)
+        self.bins = self.channels // 2 + 1 - self.first_bin if bins is None else int(bins)
+        self._i16 = False
+        if not all(0 <= v < 1 << 32 for v in (self.channels, self.hop, self.first_bin, self.bins)):
+            raise IfFirError("if_fir_rpfb_init: channels, hop, first_bin and bins must be unsigned 32-bit integers")
+        cfg = RpfbConfig(self.channels, self.hop, self.first_bin, self.bins)
+        if not self._L.if_fir_rpfb_init(ctypes.byref(self._ctx), ctypes.byref(cfg), _f32p(taps) if taps.size else None, taps.size,
+                                        int(max_samples), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._c("last_error")(None).decode())
+
+    def frame_count(self, samples):
+        """if_fir_rpfb_frame_count(): frames of a call with `samples` samples at the current stream position."""
+        return int(self._L.if_fir_rpfb_frame_count(self._ctx, int(samples)))
+
+    def _host_input(self, r):
+        """(contiguous float32 -- or int16 after set_input_format(INPUT_I16) -- array of REAL samples, sample count)"""
+        r = np.ascontiguousarray(r, dtype=np.int16 if self._i16 else np.float32).reshape(-1)
+        return r, r.size
+
+    def process(self, r):
+        """if_fir_rpfb_process(): host float32 (or int16 after set_input_format(INPUT_I16)) real samples in; returns the
+        (frames, bins) complex64 array."""
+        r, n = self._host_input(r)
+        frames = self.frame_count(n)
+        out = np.empty((frames, self.bins), dtype=np.complex64)
+        m = ctypes.c_uint64(0)
+        dummy = np.zeros(2, dtype=np.float32)
+        self._check(self._L.if_fir_rpfb_process(self._ctx, ctypes.c_void_p(r.ctypes.data if n else dummy.ctypes.data),
+                                                _f32p(out.view(np.float32) if out.size else dummy), n, ctypes.byref(m)))
+        assert m.value == frames
+        return out
+
+    def process_device(self, dev_in, dev_out, samples):
+        """if_fir_rpfb_process_device(): raw device pointers (ints), asynchronous.  Returns the frames emitted."""
+        m = ctypes.c_uint64(0)
+        self._check(self._L.if_fir_rpfb_process_device(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
+                                                       int(samples), ctypes.byref(m)))
+        return int(m.value)
+
+    def debug_config(self, grid_limit=0, position=None):
+        """if_fir_debug_rpfb_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
+        launcher's choice); position (optional) = the absolute index of the next call's first sample, with the history zeroed.
+        Returns the consecutive frames one workgroup owns."""
+        if not self._dev:
+            raise IfFirError("if_fir_debug_rpfb_config is in the development library only: construct with dev=True")
+        group = ctypes.c_uint32(0)
+        self._check(self._L.if_fir_debug_rpfb_config(self._ctx, int(grid_limit), ctypes.byref(group),
+                                                     self.NO_POSITION if position is None else int(position)))
         self._grid_limit = int(grid_limit)
         return int(group.value)
 
