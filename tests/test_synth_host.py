@@ -2,7 +2,9 @@
 call and chunk planning, the tap table and the mirrored places of qo-100-tools_amd/csrc/if_fir_synth_plan.h through the
 stand-alone checker tests/c/synth_plan_check.cpp, against Python-integer arithmetic; the fold form of tests/synth_ref.py against
 the definition (the channel combiner's, centres on the grid); the analysis-then-synthesis transfer formula against the two
-fold forms in sequence; the complex64 model against half the GPU test's bound; the compiled kernels' resources."""
+fold forms in sequence; the complex64 model against half the GPU test's bound; the depth cases of
+tests/test_synth_matrix_gpu.py against the plan, a model of the ring kernel's walk against the model, and that model's
+switchable faults against those cases; the compiled kernels' resources."""
 import os
 import re
 import subprocess
@@ -13,7 +15,7 @@ import pytest
 import pfb_ref
 import synth_ref
 from matrix_util import TOL, row_edge_taps, signal
-from test_synth_gpu import MATRIX, stream_frames
+from test_synth_gpu import MATRIX, RING_CASES, stream_frames
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "qo-100-tools_amd", "csrc")
@@ -224,6 +226,135 @@ def test_model_meets_half_the_bound(oracle):
                 worst[name] = max(worst[name], (v, (M, T, L, i16)))
             assert l2 <= TOL / 2 and mx <= TOL / 2, (M, T, L, i16, l2, mx)
     print("synth model worst l2=%.3g at %s, max=%.3g at %s" % (worst["l2"] + worst["max"]))
+
+
+def test_depth_cases_against_the_plan(plan_check):
+    """tests/synth_ref.DEPTH_CASES against if_fir_synth_plan.h: every shape is legal with the J it is listed for, the ring's
+    bytes and the two fits are synth_ref.lds_route_fits', and per size the list holds the largest J the plan itself sends
+    through the ring with the one after it, the largest J the ring can be forced at with the one after it, J = 1 and J = 32 --
+    so a change of the LDS rules cannot empty a class unnoticed"""
+    cases = synth_ref.DEPTH_CASES
+    assert len(cases) == 118 and {M for M, _, _ in cases} == set(synth_ref.SIZES)
+    got = ask(plan_check, ["config %d %d %d" % c for c in cases] + ["shape %d %d %d" % c for c in cases] +
+              ["route %d %d %d %d" % (c + (r,)) for c in cases for r in (0, 2)])
+    configs, shapes, routes = got[:len(cases)], got[len(cases):2 * len(cases)], got[2 * len(cases):]
+    assert len(routes) == 2 * len(cases)
+    plan, forced = {}, {}
+    for k, (M, T, L) in enumerate(cases):
+        J, B = synth_ref.terms(T, L), synth_ref.batch(M)
+        assert configs[k] == [str(J)] and J in synth_ref.DEPTH_J[M], (M, T, L)
+        batch, _, _, ring, fits, route, per_cu = (int(v) for v in shapes[k])
+        assert batch == B and ring == (-(-(J - 1) // B) + 1) * B * M * 8 + 10 * M
+        assert fits == int(synth_ref.lds_route_fits(M, T, L)) and (route == 2) == synth_ref.lds_route_fits(M, T, L, 4) == (per_cu >= 4)
+        assert routes[2 * k] == [str(route)] and routes[2 * k + 1] == ["2" if fits else "0"]
+        assert plan.setdefault((M, J), route) == route and forced.setdefault((M, J), fits) == fits   # the two shapes of a pair agree
+    assert sum(forced[M, J] for M, T, L in cases for J in [synth_ref.terms(T, L)]) == 98
+    for M in synth_ref.SIZES:
+        Js = synth_ref.DEPTH_J[M]
+        assert {1, 2, 32} <= set(Js) and sorted(plan[M, J] for J in Js) == [plan[M, J] for J in Js][::-1]   # the ring first, then never again
+        last4 = max([J for J in Js if plan[M, J] == 2], default=0)
+        last2 = max(J for J in Js if forced[M, J])
+        assert last4 == 32 or last4 + 1 in Js, M             # either side of the plan's switch (M = 64: the ring throughout)
+        assert last2 == 32 or last2 + 1 in Js, M             # either side of the ring's limit
+        assert (last4, last2) == {64: (32, 32), 128: (25, 32), 256: (13, 32), 512: (7, 17), 1024: (3, 8), 2048: (1, 3), 4096: (0, 1)}[M]
+        B = synth_ref.batch(M)
+        assert {J for J in (B, B + 1, 2 * B, 2 * B + 1) if J <= 32} <= set(Js)   # either side of the ring's second and third batch
+    for M, T, L in synth_ref.RING_STEP_CASES:
+        J, B = synth_ref.terms(T, L), synth_ref.batch(M)
+        assert forced[M, J] and ((J - 1) % B == 0 or not forced[M, J + 1]), (M, J)   # J on a step of NB, or the most that fits
+    assert sorted({synth_ref.batch(M) for M, _, _ in synth_ref.RING_STEP_CASES}) == [1, 2, 4, 8, 16]
+
+
+def _depth_inputs(oracle, M, T, L, i16=False):
+    F = stream_frames(M, T, L)
+    return row_edge_taps(T, L, False), synth_ref.as_frames(signal(oracle, F * M, i16)[1], M)
+
+
+def _max_metric(oracle, y, ref):
+    return oracle.err_metrics(synth_ref.iq(y), synth_ref.iq(ref))[1]
+
+
+def test_model_meets_half_the_bound_on_the_depth_cases(oracle):
+    """test_model_meets_half_the_bound's loop over tests/synth_ref.DEPTH_CASES, with the frames tests/test_synth_matrix_gpu.py
+    feeds: the complex64 model within 5e-7 of float64 in both metrics, float32 and int16 input."""
+    worst = {"l2": (0.0, None), "max": (0.0, None)}
+    for M, T, L in synth_ref.DEPTH_CASES:
+        for i16 in (False, True):
+            h, X = _depth_inputs(oracle, M, T, L, i16)
+            l2, mx = oracle.err_metrics(synth_ref.iq(synth_ref.model_c64(h, X, M, L)), synth_ref.iq(synth_ref.fold_f64(h, X, M, L)))
+            for name, v in (("l2", l2), ("max", mx)):
+                worst[name] = max(worst[name], (v, (M, T, L, i16)))
+            assert l2 <= TOL / 2 and mx <= TOL / 2, (M, T, L, i16, l2, mx)
+    print("synth depth model worst l2=%.3g at %s, max=%.3g at %s" % (worst["l2"] + worst["max"]))
+
+
+RING_DEPTH_CASES = tuple(c for c in synth_ref.DEPTH_CASES if synth_ref.lds_route_fits(*c))
+
+
+def _two_calls(h, X, M, L, cut, fault=None):
+    """the second of two calls, X[cut:], with the J - 1 frames before it as its history, in one run"""
+    J = synth_ref.terms(h.size, L)
+    assert cut >= J - 1
+    return synth_ref.ring_model_c64(h, X[cut:], M, L, X.shape[0], hist_frames=X[cut - (J - 1):cut], fault=fault, first=cut)
+
+
+def test_ring_model_is_the_model_bit_for_bit(oracle):
+    """synth_ref.ring_model_c64 -- runs, ring slots, warm-up, back / slot / fb as synth_ring_kernel has them -- gives
+    model_c64's bits on every depth case the ring takes: one batch a run, two, the whole call in one run, and a call that
+    follows another with its last J - 1 frames as the history"""
+    assert len(RING_DEPTH_CASES) == 98
+    for M, T, L in RING_DEPTH_CASES:
+        h, X = _depth_inputs(oracle, M, T, L)
+        want = synth_ref.model_c64(h, X, M, L)
+        batches = -(-X.shape[0] // synth_ref.batch(M))
+        assert batches > 4
+        for run_len in (1, 2, batches):
+            assert np.array_equal(synth_ref.ring_model_c64(h, X, M, L, run_len).view(np.uint32), want.view(np.uint32)), (M, T, L, run_len)
+        cut = X.shape[0] // 3 + 1
+        assert np.array_equal(_two_calls(h, X, M, L, cut).view(np.uint32), want[cut * L:].view(np.uint32)), (M, T, L)
+
+
+def test_ring_faults_move_the_named_cases(oracle):
+    """one fault of the ring's index algebra at a time (synth_ref.RING_FAULTS), max metric against float64 over the walk's
+    output: more than 100 x the GPU tests' bound on the cases named here, the model's own bits on the others.
+    back_on_multiple: every shape with J >= B + 1, none with J <= B; last_term_dropped: the B shapes from J = 2 (T < J L);
+    warmup_short: every walk of one batch a run from J = 2, and no walk of a zero-history call in one run; history_ignored: the
+    second of two calls from J = 2.  J = 1 has no ring depth, no warm-up and no history: no fault touches it.
+    The same for back_on_multiple on tests/test_synth_gpu.RING_CASES: its (M, J) from J = B + 1 -- (128, 16), (128, 30),
+    (64, 32), every M >= 256 -- would have noticed that fault too; (64, 6), (64, 11), (64, 16) and (128, 6) could not."""
+    loud = 100 * TOL
+    moved = {f: 0 for f in synth_ref.RING_FAULTS}
+    for M, T, L in RING_DEPTH_CASES:
+        h, X = _depth_inputs(oracle, M, T, L)
+        J, B = synth_ref.terms(T, L), synth_ref.batch(M)
+        ref, clean = synth_ref.fold_f64(h, X, M, L), synth_ref.model_c64(h, X, M, L)
+        F = X.shape[0]
+        cut = F // 3 + 1
+        walks = {"back_on_multiple": (lambda f: synth_ref.ring_model_c64(h, X, M, L, F, fault=f), J >= B + 1, 0),
+                 "last_term_dropped": (lambda f: synth_ref.ring_model_c64(h, X, M, L, 2, fault=f), T < J * L, 0),
+                 "warmup_short": (lambda f: synth_ref.ring_model_c64(h, X, M, L, 1, fault=f), J >= 2, 0),
+                 "history_ignored": (lambda f: _two_calls(h, X, M, L, cut, f), J >= 2, cut * L)}
+        for fault, (walk, moves, at) in walks.items():
+            y = walk(fault)
+            if moves:
+                assert _max_metric(oracle, y, ref[at:]) > loud, (fault, M, T, L)
+                moved[fault] += 1
+            else:
+                assert np.array_equal(y, clean[at:]), (fault, M, T, L)
+        assert np.array_equal(synth_ref.ring_model_c64(h, X, M, L, F, fault="warmup_short"), clean), (M, T, L)
+    assert moved == {"back_on_multiple": 64, "last_term_dropped": 42, "warmup_short": 84, "history_ignored": 84}, moved
+    seen = set()
+    for M, T, L in RING_CASES:
+        h, X = _depth_inputs(oracle, M, T, L)
+        J, B = synth_ref.terms(T, L), synth_ref.batch(M)
+        y = synth_ref.ring_model_c64(h, X, M, L, X.shape[0], fault="back_on_multiple")
+        if J >= B + 1:
+            assert _max_metric(oracle, y, synth_ref.fold_f64(h, X, M, L)) > loud, (M, T, L)
+        else:
+            assert np.array_equal(y, synth_ref.model_c64(h, X, M, L)), (M, T, L)
+        seen.add((M, J, J >= B + 1))
+    assert {(64, 6, False), (64, 11, False), (64, 16, False), (128, 6, False), (64, 32, True), (128, 16, True), (128, 30, True),
+            (512, 6, True), (1024, 6, True)} <= seen and not [c for c in seen if c[0] >= 256 and not c[2]]
 
 
 def test_synth_kernels_use_no_scratch():
