@@ -748,6 +748,55 @@ uint8_t if_fir_rpfb_process(if_fir_rpfb_t *pCtx, const void *pIn, float *pfIQOut
  * pDevOut holds if_fir_rpfb_frame_count() x ulBins samples */
 uint8_t if_fir_rpfb_process_device(if_fir_rpfb_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullSamples, uint64_t *pullFrames);
 
+/* ---- real-output polyphase synthesis bank (docs/SPEC.md §18; BUILD-DEFINED) ----------------------------------------------------
+ * The M/2 + 1 distinct channels of a uniform grid to ONE REAL sample stream in ONE pass, M = 128 .. 8192: the real part of the
+ * bank of if_fir_synth_t fed the Hermitian extension of each frame (channel M - k = conj of channel k), without writing the
+ * extension, transforming M points or emitting a complex stream.  By definition the sum of the up-converters of SPEC §11
+ * (if_fir_duc_t) with phase word k * 2^32 / M, the real prototype h[0..T-1] (T <= 16 M, ceil(T / L) <= 32) and factor L = ulHop
+ * (1 <= L <= M, any integer), channels 0 and M/2 once and every channel between them twice:
+ *     y[n] = sum_m h[n - m*L] ( Re X_0[m] + (-1)^n Re X_{M/2}[m] + 2 sum_{0<k<M/2} Re( X_k[m] exp(+j 2 pi k n / M) ) ),
+ *     n = absolute output index since init/reset,   X_k[m<0] = 0
+ * The imaginary parts of channels 0 and M/2 are ignored.  Input is frame-major, the output layout of if_fir_rpfb_t:
+ * in[m*ulBins + j] = channel ulFirstBin + j of frame m, complex64 or int16 pairs; channels outside the span are 0.  F frames in
+ * give exactly F*L real samples out, float32 or (if_fir_rsynth_set_output_format) int16.
+ * process(a||b) == process(a); process(b), bit for bit, wherever the frames are cut.
+ * Errors: 0 + if_fir_rsynth_last_error(); a failed call leaves the context usable and its stream position unchanged.
+ * Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_rsynth if_fir_rsynth_t;
+
+typedef struct
+{
+    uint32_t ulChannels; /* M: 128, 256, 512, 1024, 2048, 4096 or 8192 */
+    uint32_t ulHop;      /* L: output samples per frame, 1..M */
+    uint32_t ulFirstBin; /* first input channel, 0 <= ulFirstBin */
+    uint32_t ulBins;     /* input channels per frame, >= 1; ulFirstBin + ulBins <= M/2 + 1: the span does not wrap */
+} if_fir_rsynth_config_t;
+
+/* pfTaps: ulTaps real float32 taps, 1 <= ulTaps <= 16 M and ceil(ulTaps / L) <= 32, used as given (no 1/M, no gain of L).
+ * ullMaxFrames: 1..2^32, the most frames of one call */
+uint8_t if_fir_rsynth_init(if_fir_rsynth_t **ppCtx, const if_fir_rsynth_config_t *pCfg, const float *pfTaps, uint32_t ulTaps,
+                           uint64_t ullMaxFrames, int32_t lDevice);
+void if_fir_rsynth_destroy(if_fir_rsynth_t *pCtx);
+/* zero the history and the stream position */
+uint8_t if_fir_rsynth_reset(if_fir_rsynth_t *pCtx);
+/* IF_FIR_INPUT_F32 or IF_FIR_INPUT_I16 (value = int16 * 2^-15); the history is float32, so a change keeps the stream */
+uint8_t if_fir_rsynth_set_input_format(if_fir_rsynth_t *pCtx, uint32_t ulFormat);
+/* IF_FIR_OUTPUT_F32 (4 bytes per sample, the default) or IF_FIR_OUTPUT_I16 (2 bytes: the same float32 result * 2^15, rounded
+ * to nearest even, saturated at -32768 / 32767); a change keeps the stream */
+uint8_t if_fir_rsynth_set_output_format(if_fir_rsynth_t *pCtx, uint32_t ulFormat);
+uint8_t if_fir_rsynth_set_stream(if_fir_rsynth_t *pCtx, void *pStream);
+uint8_t if_fir_rsynth_synchronize(if_fir_rsynth_t *pCtx);
+const char *if_fir_rsynth_last_error(const if_fir_rsynth_t *pCtx);
+/* samples a call with ullFrames frames would emit at the current stream position: ullFrames * L (0 when the call would be refused
+ * because its last output index would pass 2^64) */
+uint64_t if_fir_rsynth_sample_count(const if_fir_rsynth_t *pCtx, uint64_t ullFrames);
+/* host pointers, synchronous; ullFrames <= ullMaxFrames of init; pFramesIn holds ullFrames x ulBins elements, pOut
+ * if_fir_rsynth_sample_count() real samples in the output format; *pullSamples (may be NULL) receives the samples emitted */
+uint8_t if_fir_rsynth_process(if_fir_rsynth_t *pCtx, const void *pFramesIn, void *pOut, uint64_t ullFrames, uint64_t *pullSamples);
+/* device pointers aligned to one element (input 8 bytes, 4 for int16; output 4 bytes, 2 for int16), asynchronous on the
+ * context's stream */
+uint8_t if_fir_rsynth_process_device(if_fir_rsynth_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullFrames, uint64_t *pullSamples);
+
 #ifdef __cplusplus
 }
 #endif

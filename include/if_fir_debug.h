@@ -141,6 +141,12 @@ uint8_t if_fir_debug_sub_config(if_fir_sub_t *pCtx, uint32_t ulGridLimit, uint32
 uint8_t if_fir_debug_subup_config(if_fir_subup_t *pCtx, uint32_t ulGridLimit, uint32_t *pulTileOutputs, uint64_t ullPosition);
 /* real-input polyphase filter bank (if_fir_rpfb_t): the three arguments as if_fir_debug_pfb_config */
 uint8_t if_fir_debug_rpfb_config(if_fir_rpfb_t *pCtx, uint32_t ulGridLimit, uint32_t *pulGroupFrames, uint64_t ullPosition);
+/* real-output polyphase synthesis bank (if_fir_rsynth_t): ulGridLimit as if_fir_debug_resamp_config, for every kernel of a
+ * call; an ullPosition other than UINT64_MAX sets the context's absolute FRAME index (the index of the next call's first frame)
+ * and zeroes its history */
+uint8_t if_fir_debug_rsynth_config(if_fir_rsynth_t *pCtx, uint32_t ulGridLimit, uint64_t ullPosition);
+/* as if_fir_debug_synth_workspace; a transformed frame takes 4 M bytes here */
+uint8_t if_fir_debug_rsynth_workspace(if_fir_rsynth_t *pCtx, uint64_t ullBytes, uint64_t *pullFrames);
 
 #ifdef __cplusplus
 }

@@ -65,6 +65,9 @@ EXPORTS = [
     "if_fir_subup_process", "if_fir_subup_process_device",
     "if_fir_rpfb_init", "if_fir_rpfb_destroy", "if_fir_rpfb_reset", "if_fir_rpfb_set_input_format", "if_fir_rpfb_set_stream",
     "if_fir_rpfb_synchronize", "if_fir_rpfb_last_error", "if_fir_rpfb_frame_count", "if_fir_rpfb_process", "if_fir_rpfb_process_device",
+    "if_fir_rsynth_init", "if_fir_rsynth_destroy", "if_fir_rsynth_reset", "if_fir_rsynth_set_input_format", "if_fir_rsynth_set_output_format",
+    "if_fir_rsynth_set_stream", "if_fir_rsynth_synchronize", "if_fir_rsynth_last_error", "if_fir_rsynth_sample_count", "if_fir_rsynth_process",
+    "if_fir_rsynth_process_device",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
@@ -75,7 +78,8 @@ DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_ta
                "if_fir_debug_combiner_config", "if_fir_debug_combiner_seek", "if_fir_debug_combiner_tables",
                "if_fir_debug_ddc_config", "if_fir_debug_duc_config", "if_fir_debug_arb_config",
                "if_fir_debug_pfb_config", "if_fir_debug_synth_config", "if_fir_debug_synth_workspace",
-               "if_fir_debug_sub_config", "if_fir_debug_subup_config", "if_fir_debug_rpfb_config"]
+               "if_fir_debug_sub_config", "if_fir_debug_subup_config", "if_fir_debug_rpfb_config",
+               "if_fir_debug_rsynth_config", "if_fir_debug_rsynth_workspace"]
 MC_ID_BYTES = 128
 
 
@@ -92,6 +96,11 @@ class PfbConfig(ctypes.Structure):
 
 class RpfbConfig(ctypes.Structure):
     """if_fir_rpfb_config_t"""
+    _fields_ = [("ulChannels", ctypes.c_uint32), ("ulHop", ctypes.c_uint32), ("ulFirstBin", ctypes.c_uint32), ("ulBins", ctypes.c_uint32)]
+
+
+class RsynthConfig(ctypes.Structure):
+    """if_fir_rsynth_config_t"""
     _fields_ = [("ulChannels", ctypes.c_uint32), ("ulHop", ctypes.c_uint32), ("ulFirstBin", ctypes.c_uint32), ("ulBins", ctypes.c_uint32)]
 
 
@@ -221,7 +230,7 @@ def _load(path, dev):
     L.if_fir_mc_get_chunk_samples.restype = u8
     # the streaming contexts (_StreamCtx): what the families declare alike, then what each has of its own
     for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_", "if_fir_ddc_", "if_fir_duc_", "if_fir_arb_",
-                   "if_fir_pfb_", "if_fir_synth_", "if_fir_sub_", "if_fir_subup_", "if_fir_rpfb_"):
+                   "if_fir_pfb_", "if_fir_synth_", "if_fir_sub_", "if_fir_subup_", "if_fir_rpfb_", "if_fir_rsynth_"):
         for name, args, res in (("destroy", [vp], None), ("reset", [vp], u8), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
                                 ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p)):
             getattr(L, prefix + name).argtypes = args
@@ -337,7 +346,21 @@ def _load(path, dev):
     L.if_fir_rpfb_process.restype = u8
     L.if_fir_rpfb_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.if_fir_rpfb_process_device.restype = u8
+    L.if_fir_rsynth_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(RsynthConfig), f32p, u32, u64, i32]
+    L.if_fir_rsynth_init.restype = u8
+    L.if_fir_rsynth_set_output_format.argtypes = [vp, u32]
+    L.if_fir_rsynth_set_output_format.restype = u8
+    L.if_fir_rsynth_sample_count.argtypes = [vp, u64]
+    L.if_fir_rsynth_sample_count.restype = u64
+    L.if_fir_rsynth_process.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.if_fir_rsynth_process.restype = u8
+    L.if_fir_rsynth_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.if_fir_rsynth_process_device.restype = u8
     if dev:
+        L.if_fir_debug_rsynth_config.argtypes = [vp, u32, u64]
+        L.if_fir_debug_rsynth_config.restype = u8
+        L.if_fir_debug_rsynth_workspace.argtypes = [vp, u64, ctypes.POINTER(u64)]
+        L.if_fir_debug_rsynth_workspace.restype = u8
         L.if_fir_debug_rpfb_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
         L.if_fir_debug_rpfb_config.restype = u8
         L.if_fir_debug_subup_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
@@ -620,8 +643,8 @@ class IfFir:
 
 
 class _StreamCtx:
-    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb, IfFirSynth, IfFirSub, IfFirSubUp and IfFirRpfb share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
-    calls the twelve families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
+    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb, IfFirSynth, IfFirSub, IfFirSubUp, IfFirRpfb and IfFirRsynth share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
+    calls the thirteen families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
     __init__, self._L, self._ctx and self._i16."""
     _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
 
@@ -1382,6 +1405,88 @@ class IfFirSynth(_StreamCtx):
         self._need_dev("if_fir_debug_synth_workspace")
         got = ctypes.c_uint64(0)
         self._check(self._L.if_fir_debug_synth_workspace(self._ctx, int(nbytes), ctypes.byref(got)))
+        return int(got.value)
+
+
+class IfFirRsynth(_StreamCtx):
+    """One if_fir_rsynth_t: the `channels` / 2 + 1 distinct channels of a uniform grid to one REAL stream in one pass, `hop` real
+    output samples per frame of `bins` values (docs/SPEC.md §18).  Methods mirror the C entry points; its input is what
+    IfFirRpfb.process returns, its output float32 or (after set_output_format(OUTPUT_I16)) int16."""
+    _PREFIX = "if_fir_rsynth_"
+    NO_POSITION = (1 << 64) - 1
+
+    def __init__(self, taps, channels, hop=None, first_bin=0, bins=None, max_frames=1 << 12, device=0, dev=False):
+        self._L = dev_lib() if dev else lib()
+        self._ctx = ctypes.c_void_p()
+        self._dev = bool(dev)
+        taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        self.taps = taps
+        self.channels = int(channels)
+        self.hop = self.channels if hop is None else int(hop)
+        self.first_bin = int(first_bin)
+        self.bins = self.channels // 2 + 1 - self.first_bin if bins is None else int(bins)
+        self._i16 = self._o16 = False
+        if not all(0 <= v < 1 << 32 for v in (self.channels, self.hop, self.first_bin, self.bins)):
+            raise IfFirError("if_fir_rsynth_init: channels, hop, first_bin and bins must be unsigned 32-bit integers")
+        cfg = RsynthConfig(self.channels, self.hop, self.first_bin, self.bins)
+        if not self._L.if_fir_rsynth_init(ctypes.byref(self._ctx), ctypes.byref(cfg), _f32p(taps) if taps.size else None, taps.size,
+                                          int(max_frames), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._c("last_error")(None).decode())
+
+    def set_output_format(self, fmt):
+        """if_fir_rsynth_set_output_format(): OUTPUT_F32 or OUTPUT_I16 (the float32 result times 2^15, to nearest even, saturated)."""
+        self._check(self._L.if_fir_rsynth_set_output_format(self._ctx, int(fmt)))
+        self._o16 = (int(fmt) == OUTPUT_I16)
+
+    def sample_count(self, frames):
+        """if_fir_rsynth_sample_count(): output samples of a call with `frames` frames at the current stream position."""
+        return int(self._L.if_fir_rsynth_sample_count(self._ctx, int(frames)))
+
+    def _frames_input(self, frames):
+        """(contiguous array, frame count) of a host (frames, bins) array: complex64 / interleaved float32, or int16 pairs after
+        set_input_format(INPUT_I16)"""
+        x, n = self._host_input(frames)
+        if n % self.bins:
+            raise IfFirError("if_fir_rsynth_process: %d elements are not whole frames of %d bins" % (n, self.bins))
+        return x, n // self.bins
+
+    def process(self, frames):
+        """if_fir_rsynth_process(): a host (frames, bins) array in (what IfFirRpfb.process returns); real float32 (or int16 after
+        set_output_format(OUTPUT_I16)) out."""
+        x, f = self._frames_input(frames)
+        out = np.empty(f * self.hop, dtype=np.int16 if self._o16 else np.float32)
+        m = ctypes.c_uint64(0)
+        dummy = np.zeros(2, dtype=np.float32)
+        self._check(self._L.if_fir_rsynth_process(self._ctx, ctypes.c_void_p(x.ctypes.data if f else dummy.ctypes.data),
+                                                  ctypes.c_void_p(out.ctypes.data if out.size else dummy.ctypes.data), f, ctypes.byref(m)))
+        assert m.value == out.size
+        return out
+
+    def process_device(self, dev_in, dev_out, frames):
+        """if_fir_rsynth_process_device(): raw device pointers (ints), asynchronous.  Returns the samples emitted."""
+        m = ctypes.c_uint64(0)
+        self._check(self._L.if_fir_rsynth_process_device(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
+                                                         int(frames), ctypes.byref(m)))
+        return int(m.value)
+
+    def _need_dev(self, name):
+        if not self._dev:
+            raise IfFirError("%s is in the development library only: construct with dev=True" % name)
+
+    def debug_config(self, grid_limit=0, position=None):
+        """if_fir_debug_rsynth_config() (development library: construct with dev=True): at most grid_limit workgroups per kernel
+        (0 = the launcher's choice); position (optional) = the absolute index of the next call's first FRAME, with the history
+        zeroed."""
+        self._need_dev("if_fir_debug_rsynth_config")
+        self._check(self._L.if_fir_debug_rsynth_config(self._ctx, int(grid_limit), self.NO_POSITION if position is None else int(position)))
+
+    def debug_workspace(self, nbytes=0):
+        """if_fir_debug_rsynth_workspace() (development library): nbytes > 0 replaces the workspace by one of that budget.
+        Returns the frames of a call one chunk emits the outputs of."""
+        self._need_dev("if_fir_debug_rsynth_workspace")
+        got = ctypes.c_uint64(0)
+        self._check(self._L.if_fir_debug_rsynth_workspace(self._ctx, int(nbytes), ctypes.byref(got)))
         return int(got.value)
 
 
