@@ -797,6 +797,56 @@ uint8_t if_fir_rsynth_process(if_fir_rsynth_t *pCtx, const void *pFramesIn, void
  * context's stream */
 uint8_t if_fir_rsynth_process_device(if_fir_rsynth_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullFrames, uint64_t *pullSamples);
 
+/* ---- frame power stage: filter-bank frames to detector spectrum codes (docs/SPEC.md §19; BUILD-DEFINED) ------------------------
+ * Frames in the banks' layout in (in[a*ulBins + i], what if_fir_pfb_t, if_fir_rpfb_t and if_fir_sub_t emit), K-frame averages of
+ * |.|^2 per output bin out, as the uint16 spectrum codes wb_detect_frames_device() reads (the mapping of if_fir_psd_t) and,
+ * optionally, as float32 powers: the polyphase spectrometer of a stream whose bank is already running, without a second pass
+ * over the samples and without a transform.  Output bin j sums the G adjacent elements ulFirst + j*G .. ulFirst + j*G + G - 1;
+ * output frame f averages the input frames f*K .. f*K + K - 1 (a = absolute frame index since init/reset):
+ *     P[f][j] = ( sum_{a in frame f} sum_{g<G} |in[a*B + ulFirst + j*G + g]|^2 ) / (K * G * fNorm)
+ * in float32, in the order SPEC §19 fixes; the code of P is that of SPEC §8 with fRefPower.  A call with F frames at position c
+ * emits floor((c+F)/K) - floor(c/K) output frames (possibly none); what it leaves open is carried as sums, not as samples.
+ * Input complex64 or int16 pairs (value = int16 * 2^-15).
+ * process(a||b) == process(a); process(b), bit for bit in both outputs, wherever the frames are cut.
+ * Errors: 0 + if_fir_fpow_last_error(); a failed call leaves the context usable and its stream position unchanged.
+ * Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_fpow if_fir_fpow_t;
+
+typedef struct
+{
+    uint32_t ulBins;        /* B: elements per input frame, 1..8192 (if_fir_rpfb_t at M = 8192 emits 4097) */
+    uint32_t ulFirst;       /* first element of a frame that is used */
+    uint32_t ulGroup;       /* G: adjacent elements summed into one output bin, 1..64 */
+    uint32_t ulOutBins;     /* Bo >= 1, ulFirst + G*Bo <= B */
+    uint32_t ulFrames;      /* K: input frames averaged per output frame, 1..65535 */
+    float fNorm;            /* > 0, finite: sum h^2 of the bank's prototype makes white noise of variance s^2 read s^2 */
+    float fRefPower;        /* > 0, finite: as if_fir_psd_config_t */
+    uint32_t ulInputFormat; /* IF_FIR_INPUT_F32 (complex64) or IF_FIR_INPUT_I16 (int16 pairs * 2^-15) */
+} if_fir_fpow_config_t;
+
+/* ullMaxFrames: 1..2^32, the most input frames of one call (host or device pointers); refused where the chunk sums of such a
+ * call would pass 2^29 float32 values */
+uint8_t if_fir_fpow_init(if_fir_fpow_t **ppCtx, const if_fir_fpow_config_t *pCfg, uint64_t ullMaxFrames, int32_t lDevice);
+void if_fir_fpow_destroy(if_fir_fpow_t *pCtx);
+/* zero the stream position (and with it what is carried) */
+uint8_t if_fir_fpow_reset(if_fir_fpow_t *pCtx);
+/* IF_FIR_INPUT_F32 or IF_FIR_INPUT_I16; what is carried is float32 sums, so a change keeps the stream */
+uint8_t if_fir_fpow_set_input_format(if_fir_fpow_t *pCtx, uint32_t ulFormat);
+uint8_t if_fir_fpow_set_stream(if_fir_fpow_t *pCtx, void *pStream);
+uint8_t if_fir_fpow_synchronize(if_fir_fpow_t *pCtx);
+const char *if_fir_fpow_last_error(const if_fir_fpow_t *pCtx);
+/* output frames a call with ullFrames frames would emit at the current stream position (0 when the call would be refused because
+ * the position would pass 2^64) */
+uint64_t if_fir_fpow_frame_count(const if_fir_fpow_t *pCtx, uint64_t ullFrames);
+/* host pointers, synchronous; ullFrames <= ullMaxFrames of init; pFramesIn holds ullFrames x ulBins elements, pusBins
+ * if_fir_fpow_frame_count() x ulOutBins codes, pfPower (may be NULL) as many float32 powers; *pulOutFrames (may be NULL) receives
+ * the frames emitted */
+uint8_t if_fir_fpow_process(if_fir_fpow_t *pCtx, const void *pFramesIn, uint64_t ullFrames, uint16_t *pusBins, float *pfPower,
+                            uint32_t *pulOutFrames);
+/* device pointers aligned to one element (input 8 bytes, 4 for int16; codes 2; powers 4), asynchronous on the context's stream */
+uint8_t if_fir_fpow_process_device(if_fir_fpow_t *pCtx, const void *pDevIn, uint64_t ullFrames, uint16_t *pusDevBins, float *pfDevPower,
+                                   uint32_t *pulOutFrames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,10 @@ uint8_t if_fir_debug_rpfb_config(if_fir_rpfb_t *pCtx, uint32_t ulGridLimit, uint
 uint8_t if_fir_debug_rsynth_config(if_fir_rsynth_t *pCtx, uint32_t ulGridLimit, uint64_t ullPosition);
 /* as if_fir_debug_synth_workspace; a transformed frame takes 4 M bytes here */
 uint8_t if_fir_debug_rsynth_workspace(if_fir_rsynth_t *pCtx, uint64_t ullBytes, uint64_t *pullFrames);
+/* frame power stage (if_fir_fpow_t): ulGridLimit as if_fir_debug_resamp_config, for both kernels of a call; an ullPosition other
+ * than UINT64_MAX sets the context's absolute input FRAME index (the index of the next call's first frame) and clears what is
+ * carried: the open frame's accumulator and the open chunk's partial sum start from +0 there */
+uint8_t if_fir_debug_fpow_config(if_fir_fpow_t *pCtx, uint32_t ulGridLimit, uint64_t ullPosition);
 
 #ifdef __cplusplus
 }

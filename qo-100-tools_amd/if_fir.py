@@ -68,6 +68,8 @@ EXPORTS = [
     "if_fir_rsynth_init", "if_fir_rsynth_destroy", "if_fir_rsynth_reset", "if_fir_rsynth_set_input_format", "if_fir_rsynth_set_output_format",
     "if_fir_rsynth_set_stream", "if_fir_rsynth_synchronize", "if_fir_rsynth_last_error", "if_fir_rsynth_sample_count", "if_fir_rsynth_process",
     "if_fir_rsynth_process_device",
+    "if_fir_fpow_init", "if_fir_fpow_destroy", "if_fir_fpow_reset", "if_fir_fpow_set_input_format", "if_fir_fpow_set_stream",
+    "if_fir_fpow_synchronize", "if_fir_fpow_last_error", "if_fir_fpow_frame_count", "if_fir_fpow_process", "if_fir_fpow_process_device",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
@@ -79,7 +81,7 @@ DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_ta
                "if_fir_debug_ddc_config", "if_fir_debug_duc_config", "if_fir_debug_arb_config",
                "if_fir_debug_pfb_config", "if_fir_debug_synth_config", "if_fir_debug_synth_workspace",
                "if_fir_debug_sub_config", "if_fir_debug_subup_config", "if_fir_debug_rpfb_config",
-               "if_fir_debug_rsynth_config", "if_fir_debug_rsynth_workspace"]
+               "if_fir_debug_rsynth_config", "if_fir_debug_rsynth_workspace", "if_fir_debug_fpow_config"]
 MC_ID_BYTES = 128
 
 
@@ -117,6 +119,12 @@ class SubConfig(ctypes.Structure):
 class SubUpConfig(ctypes.Structure):
     """if_fir_subup_config_t"""
     _fields_ = [("ulBins", ctypes.c_uint32), ("ulTaps", ctypes.c_uint32), ("ulTapRows", ctypes.c_uint32), ("ulInterpolation", ctypes.c_uint32)]
+
+
+class FpowConfig(ctypes.Structure):
+    """if_fir_fpow_config_t"""
+    _fields_ = [("ulBins", ctypes.c_uint32), ("ulFirst", ctypes.c_uint32), ("ulGroup", ctypes.c_uint32), ("ulOutBins", ctypes.c_uint32),
+                ("ulFrames", ctypes.c_uint32), ("fNorm", ctypes.c_float), ("fRefPower", ctypes.c_float), ("ulInputFormat", ctypes.c_uint32)]
 
 
 class IfFirError(RuntimeError):
@@ -230,7 +238,7 @@ def _load(path, dev):
     L.if_fir_mc_get_chunk_samples.restype = u8
     # the streaming contexts (_StreamCtx): what the families declare alike, then what each has of its own
     for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_", "if_fir_ddc_", "if_fir_duc_", "if_fir_arb_",
-                   "if_fir_pfb_", "if_fir_synth_", "if_fir_sub_", "if_fir_subup_", "if_fir_rpfb_", "if_fir_rsynth_"):
+                   "if_fir_pfb_", "if_fir_synth_", "if_fir_sub_", "if_fir_subup_", "if_fir_rpfb_", "if_fir_rsynth_", "if_fir_fpow_"):
         for name, args, res in (("destroy", [vp], None), ("reset", [vp], u8), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
                                 ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p)):
             getattr(L, prefix + name).argtypes = args
@@ -311,6 +319,17 @@ def _load(path, dev):
     L.if_fir_synth_process.restype = u8
     L.if_fir_synth_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.if_fir_synth_process_device.restype = u8
+    L.if_fir_fpow_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(FpowConfig), u64, i32]
+    L.if_fir_fpow_init.restype = u8
+    L.if_fir_fpow_frame_count.argtypes = [vp, u64]
+    L.if_fir_fpow_frame_count.restype = u64
+    L.if_fir_fpow_process.argtypes = [vp, vp, u64, u16p, f32p, ctypes.POINTER(u32)]
+    L.if_fir_fpow_process.restype = u8
+    L.if_fir_fpow_process_device.argtypes = [vp, vp, u64, vp, vp, ctypes.POINTER(u32)]
+    L.if_fir_fpow_process_device.restype = u8
+    if dev:
+        L.if_fir_debug_fpow_config.argtypes = [vp, u32, u64]
+        L.if_fir_debug_fpow_config.restype = u8
     L.if_fir_sub_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(SubConfig), f32p, u64, i32]
     L.if_fir_sub_init.restype = u8
     L.if_fir_sub_set_nco.argtypes = [vp, f64p]
@@ -643,8 +662,8 @@ class IfFir:
 
 
 class _StreamCtx:
-    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb, IfFirSynth, IfFirSub, IfFirSubUp, IfFirRpfb and IfFirRsynth share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
-    calls the thirteen families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
+    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb, IfFirSynth, IfFirSub, IfFirSubUp, IfFirRpfb, IfFirRsynth and IfFirFpow share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
+    calls the fourteen families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
     __init__, self._L, self._ctx and self._i16."""
     _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
 
@@ -1652,6 +1671,70 @@ class IfFirSubUp(_StreamCtx):
 
 
 FFT_TABLE_FLOATS = 2 * (4096 + 4096 + 256 + 1024 + 1024 + 64 + 256)
+
+
+class IfFirFpow(_StreamCtx):
+    """One if_fir_fpow_t: the power stage over frames of `bins` elements (what IfFirPfb, IfFirRpfb and IfFirSub emit): every
+    output bin sums `group` adjacent elements from `first` on, every output frame averages `frames` input frames, and the result
+    comes as the uint16 spectrum codes wb_detect reads and, optionally, as float32 powers (docs/SPEC.md §19).  Methods mirror
+    the C entry points; how many frames a call emits depends on the stream position (frame_count)."""
+    _PREFIX = "if_fir_fpow_"
+    NO_POSITION = (1 << 64) - 1
+
+    def __init__(self, bins, frames, norm=1.0, first=0, group=1, out_bins=None, ref_power=1.0, input_format=INPUT_F32,
+                 max_frames=1 << 12, device=0, dev=False):
+        self._L = dev_lib() if dev else lib()
+        self._ctx = ctypes.c_void_p()
+        self._dev = bool(dev)
+        self.bins, self.first, self.group, self.frames = int(bins), int(first), int(group), int(frames)
+        self.out_bins = int(out_bins) if out_bins is not None else (max(self.bins - self.first, 0) // self.group if self.group > 0 else 0)
+        self._i16 = (int(input_format) == INPUT_I16)
+        if not all(0 <= v < 1 << 32 for v in (self.bins, self.first, self.group, self.out_bins, self.frames, int(input_format))):
+            raise IfFirError("if_fir_fpow_init: bins, first, group, output bins, frames and format must be unsigned 32-bit integers")
+        cfg = FpowConfig(self.bins, self.first, self.group, self.out_bins, self.frames, float(norm), float(ref_power), int(input_format))
+        if not self._L.if_fir_fpow_init(ctypes.byref(self._ctx), ctypes.byref(cfg), int(max_frames), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._c("last_error")(None).decode())
+
+    def frame_count(self, frames):
+        """if_fir_fpow_frame_count(): output frames of a call with `frames` input frames at the current stream position."""
+        return int(self._L.if_fir_fpow_frame_count(self._ctx, int(frames)))
+
+    def process(self, frames, want_power=True):
+        """if_fir_fpow_process(): a host (frames, bins) array in (complex64 / interleaved float32, or int16 pairs after
+        set_input_format(INPUT_I16)); returns ((output frames, out_bins) uint16 codes, float32 powers of that shape or None)."""
+        x, n = self._host_input(frames)
+        if n % self.bins:
+            raise IfFirError("if_fir_fpow_process: %d elements are not whole frames of %d bins" % (n, self.bins))
+        f = n // self.bins
+        m_want = self.frame_count(f)
+        codes = np.empty((m_want, self.out_bins), dtype=np.uint16)
+        power = np.empty((m_want, self.out_bins), dtype=np.float32) if want_power else None
+        m = ctypes.c_uint32(0)
+        dummy = np.zeros(2, dtype=np.float32)
+        self._check(self._L.if_fir_fpow_process(
+            self._ctx, ctypes.c_void_p(x.ctypes.data if f else dummy.ctypes.data), f,
+            codes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)) if m_want else None,
+            _f32p(power) if want_power and m_want else None, ctypes.byref(m)))
+        assert m.value == m_want
+        return codes, power
+
+    def process_device(self, dev_in, frames, dev_bins, dev_power=0):
+        """if_fir_fpow_process_device(): raw device pointers (ints; dev_power may be 0), asynchronous.  Returns the frames emitted."""
+        m = ctypes.c_uint32(0)
+        self._check(self._L.if_fir_fpow_process_device(self._ctx, ctypes.c_void_p(dev_in or None), int(frames),
+                                                       ctypes.c_void_p(dev_bins or None), ctypes.c_void_p(dev_power or None),
+                                                       ctypes.byref(m)))
+        return int(m.value)
+
+    def debug_config(self, grid_limit=0, position=None):
+        """if_fir_debug_fpow_config() (development library: construct with dev=True): at most grid_limit workgroups per kernel
+        (0 = the launcher's choice); position (optional) = the absolute index of the next call's first input FRAME, with the
+        carried sums cleared."""
+        if not self._dev:
+            raise IfFirError("if_fir_debug_fpow_config is in the development library only: construct with dev=True")
+        self._check(self._L.if_fir_debug_fpow_config(self._ctx, int(grid_limit),
+                                                     self.NO_POSITION if position is None else int(position)))
 
 
 def debug_fft_tables(taps, decimation, complex_taps=False, nco_delta=0):
