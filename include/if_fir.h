@@ -847,6 +847,53 @@ uint8_t if_fir_fpow_process(if_fir_fpow_t *pCtx, const void *pFramesIn, uint64_t
 uint8_t if_fir_fpow_process_device(if_fir_fpow_t *pCtx, const void *pDevIn, uint64_t ullFrames, uint16_t *pusDevBins, float *pfDevPower,
                                    uint32_t *pulOutFrames);
 
+/* ---- corner turn: bank frames to channel streams and back (docs/SPEC.md §20; BUILD-DEFINED) ------------------------------------
+ * The frame families (if_fir_pfb_t, if_fir_rpfb_t, if_fir_sub_t, if_fir_subup_t, if_fir_synth_t, if_fir_rsynth_t, if_fir_fpow_t)
+ * read or write frames, in[a*ulBins + i]; the stream families read or write one contiguous stream per context.  This stage
+ * moves a list of bins between the two layouts on the device, with the format conversion fused, one kernel pass per direction:
+ *     IF_FIR_TURN_TO_STREAMS:  out[c*P + a] = conv(in[a*B + sel[c]])            0 <= a < F, 0 <= c < C; row tails untouched
+ *     IF_FIR_TURN_TO_FRAMES:   out[a*B + i] = conv(in[c*P + a]) if i == sel[c], +0 (all bits zero) otherwise; every element written
+ * F = frames of the call, P = row pitch in elements (a call argument, P >= F, at most 2^40: a caller appends into per-channel
+ * buffers).  conv: float32 to float32 and int16 to int16 copy the bits; int16 to float32 is the exact int16 * 2^-15; float32
+ * to int16 is times 2^15, to nearest even, saturated (+-inf saturate), NaN gives 0.  No arithmetic otherwise: bit for bit.
+ * The stage carries no state (no history, no position, no reset): process(a||b) == process(a); process(b) with the pointers
+ * advanced by hand.  Errors: 0 + if_fir_turn_last_error(); a failed call leaves the context usable.
+ * Calls on a stream that is being captured into a hipGraph are refused. */
+typedef struct if_fir_turn if_fir_turn_t;
+
+enum
+{
+    IF_FIR_TURN_TO_STREAMS = 0, /* frames in, C rows of pitch P out */
+    IF_FIR_TURN_TO_FRAMES = 1   /* C rows of pitch P in, whole frames out (unlisted bins zero) */
+};
+
+typedef struct
+{
+    uint32_t ulDirection;    /* IF_FIR_TURN_TO_STREAMS or IF_FIR_TURN_TO_FRAMES */
+    uint32_t ulBins;         /* B: elements per frame, 1..8192 */
+    uint32_t ulChannels;     /* C: channel rows, 1..B */
+    uint32_t ulFirst;        /* first bin of the span sel[c] = ulFirst + c (list pointer NULL), ulFirst + C <= B; 0 beside a list */
+    uint32_t ulInputFormat;  /* IF_FIR_INPUT_F32 (complex64) or IF_FIR_INPUT_I16 (int16 pairs * 2^-15) */
+    uint32_t ulOutputFormat; /* IF_FIR_OUTPUT_F32 (complex64) or IF_FIR_OUTPUT_I16 (int16 pairs) */
+} if_fir_turn_config_t;
+
+/* pulSel: NULL for the span, or ulChannels bin indices, each < ulBins, pairwise distinct, in any order (copied).  ullMaxFrames:
+ * 1..2^32, the most frames of one call (host or device pointers) */
+uint8_t if_fir_turn_init(if_fir_turn_t **ppCtx, const if_fir_turn_config_t *pCfg, const uint32_t *pulSel, uint64_t ullMaxFrames,
+                         int32_t lDevice);
+void if_fir_turn_destroy(if_fir_turn_t *pCtx);
+/* from the next call on */
+uint8_t if_fir_turn_set_input_format(if_fir_turn_t *pCtx, uint32_t ulFormat);
+uint8_t if_fir_turn_set_output_format(if_fir_turn_t *pCtx, uint32_t ulFormat);
+uint8_t if_fir_turn_set_stream(if_fir_turn_t *pCtx, void *pStream);
+uint8_t if_fir_turn_synchronize(if_fir_turn_t *pCtx);
+const char *if_fir_turn_last_error(const if_fir_turn_t *pCtx);
+/* host pointers, synchronous; ullFrames <= ullMaxFrames of init (0 is legal and writes nothing); the frame side holds
+ * ullFrames x ulBins elements, the row side ulChannels rows of ullPitch elements of which the first ullFrames are used */
+uint8_t if_fir_turn_process(if_fir_turn_t *pCtx, const void *pIn, void *pOut, uint64_t ullFrames, uint64_t ullPitch);
+/* device pointers aligned to one element (8 bytes, 4 for int16 pairs), asynchronous on the context's stream */
+uint8_t if_fir_turn_process_device(if_fir_turn_t *pCtx, const void *pDevIn, void *pDevOut, uint64_t ullFrames, uint64_t ullPitch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,10 @@ uint8_t if_fir_debug_rsynth_workspace(if_fir_rsynth_t *pCtx, uint64_t ullBytes, 
  * carried: the open frame's accumulator and the open chunk's partial sum start from +0 there */
 uint8_t if_fir_debug_fpow_config(if_fir_fpow_t *pCtx, uint32_t ulGridLimit, uint64_t ullPosition);
 
+/* corner turn (if_fir_turn_t): ulGridLimit as if_fir_debug_resamp_config (at most that many workgroups, 0 = the launcher's choice):
+ * a small call then walks the grid-stride loop over its tiles */
+uint8_t if_fir_debug_turn_config(if_fir_turn_t *pCtx, uint32_t ulGridLimit);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,8 @@ EXPORTS = [
     "if_fir_rsynth_process_device",
     "if_fir_fpow_init", "if_fir_fpow_destroy", "if_fir_fpow_reset", "if_fir_fpow_set_input_format", "if_fir_fpow_set_stream",
     "if_fir_fpow_synchronize", "if_fir_fpow_last_error", "if_fir_fpow_frame_count", "if_fir_fpow_process", "if_fir_fpow_process_device",
+    "if_fir_turn_init", "if_fir_turn_destroy", "if_fir_turn_set_input_format", "if_fir_turn_set_output_format", "if_fir_turn_set_stream",
+    "if_fir_turn_synchronize", "if_fir_turn_last_error", "if_fir_turn_process", "if_fir_turn_process_device",
 ]
 # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
 DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
@@ -81,7 +83,8 @@ DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_ta
                "if_fir_debug_ddc_config", "if_fir_debug_duc_config", "if_fir_debug_arb_config",
                "if_fir_debug_pfb_config", "if_fir_debug_synth_config", "if_fir_debug_synth_workspace",
                "if_fir_debug_sub_config", "if_fir_debug_subup_config", "if_fir_debug_rpfb_config",
-               "if_fir_debug_rsynth_config", "if_fir_debug_rsynth_workspace", "if_fir_debug_fpow_config"]
+               "if_fir_debug_rsynth_config", "if_fir_debug_rsynth_workspace", "if_fir_debug_fpow_config",
+               "if_fir_debug_turn_config"]
 MC_ID_BYTES = 128
 
 
@@ -125,6 +128,12 @@ class FpowConfig(ctypes.Structure):
     """if_fir_fpow_config_t"""
     _fields_ = [("ulBins", ctypes.c_uint32), ("ulFirst", ctypes.c_uint32), ("ulGroup", ctypes.c_uint32), ("ulOutBins", ctypes.c_uint32),
                 ("ulFrames", ctypes.c_uint32), ("fNorm", ctypes.c_float), ("fRefPower", ctypes.c_float), ("ulInputFormat", ctypes.c_uint32)]
+
+
+class TurnConfig(ctypes.Structure):
+    """if_fir_turn_config_t"""
+    _fields_ = [("ulDirection", ctypes.c_uint32), ("ulBins", ctypes.c_uint32), ("ulChannels", ctypes.c_uint32), ("ulFirst", ctypes.c_uint32),
+                ("ulInputFormat", ctypes.c_uint32), ("ulOutputFormat", ctypes.c_uint32)]
 
 
 class IfFirError(RuntimeError):
@@ -330,6 +339,16 @@ def _load(path, dev):
     if dev:
         L.if_fir_debug_fpow_config.argtypes = [vp, u32, u64]
         L.if_fir_debug_fpow_config.restype = u8
+    # the corner turn carries no state: the common calls but no reset
+    for name, args, res in (("destroy", [vp], None), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
+                            ("set_output_format", [vp, u32], u8), ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p),
+                            ("init", [ctypes.POINTER(vp), ctypes.POINTER(TurnConfig), ctypes.POINTER(u32), u64, i32], u8),
+                            ("process", [vp, vp, vp, u64, u64], u8), ("process_device", [vp, vp, vp, u64, u64], u8)):
+        getattr(L, "if_fir_turn_" + name).argtypes = args
+        getattr(L, "if_fir_turn_" + name).restype = res
+    if dev:
+        L.if_fir_debug_turn_config.argtypes = [vp, u32]
+        L.if_fir_debug_turn_config.restype = u8
     L.if_fir_sub_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(SubConfig), f32p, u64, i32]
     L.if_fir_sub_init.restype = u8
     L.if_fir_sub_set_nco.argtypes = [vp, f64p]
@@ -662,8 +681,8 @@ class IfFir:
 
 
 class _StreamCtx:
-    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb, IfFirSynth, IfFirSub, IfFirSubUp, IfFirRpfb, IfFirRsynth and IfFirFpow share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
-    calls the fourteen families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
+    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb, IfFirSynth, IfFirSub, IfFirSubUp, IfFirRpfb, IfFirRsynth, IfFirFpow and IfFirTurn share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
+    calls the fifteen families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
     __init__, self._L, self._ctx and self._i16."""
     _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
 
@@ -1735,6 +1754,85 @@ class IfFirFpow(_StreamCtx):
             raise IfFirError("if_fir_debug_fpow_config is in the development library only: construct with dev=True")
         self._check(self._L.if_fir_debug_fpow_config(self._ctx, int(grid_limit),
                                                      self.NO_POSITION if position is None else int(position)))
+
+
+TURN_TO_STREAMS, TURN_TO_FRAMES = 0, 1
+
+
+class IfFirTurn(_StreamCtx):
+    """One if_fir_turn_t: the corner turn between frames of `bins` elements (the layout of IfFirPfb, IfFirRpfb, IfFirSub, IfFirSubUp,
+    IfFirSynth, IfFirRsynth and IfFirFpow) and one contiguous row per listed bin (what the stream families read and write), with
+    the format conversion fused (docs/SPEC.md §20).  `sel` is a list of distinct bins in any order, or None for the span
+    first .. first + channels - 1.  The stage carries no state: there is no reset.  Methods mirror the C entry points."""
+    _PREFIX = "if_fir_turn_"
+
+    def __init__(self, direction, bins, sel=None, channels=None, first=0, input_format=INPUT_F32, output_format=OUTPUT_F32,
+                 max_frames=1 << 12, device=0, dev=False):
+        self._L = dev_lib() if dev else lib()
+        self._ctx = ctypes.c_void_p()
+        self._dev = bool(dev)
+        self.direction, self.bins, self.first = int(direction), int(bins), int(first)
+        if sel is not None:
+            sel = [int(v) for v in np.asarray(sel).reshape(-1)]
+            if not all(0 <= v < 1 << 32 for v in sel):
+                raise IfFirError("if_fir_turn_init: listed bins must be unsigned 32-bit integers")
+        self.channels = int(channels) if channels is not None else (len(sel) if sel is not None else self.bins - self.first)
+        self._i16 = (int(input_format) == INPUT_I16)
+        self._o16 = (int(output_format) == OUTPUT_I16)
+        if not all(0 <= v < 1 << 32 for v in (self.direction, self.bins, self.channels, self.first, int(input_format), int(output_format))):
+            raise IfFirError("if_fir_turn_init: direction, bins, channels, first and the formats must be unsigned 32-bit integers")
+        if sel is not None and len(sel) != self.channels:
+            raise IfFirError("if_fir_turn_init: %d listed bins for %d channels" % (len(sel), self.channels))
+        cfg = TurnConfig(self.direction, self.bins, self.channels, self.first, int(input_format), int(output_format))
+        arr = (ctypes.c_uint32 * max(len(sel), 1))(*sel) if sel is not None else None
+        if not self._L.if_fir_turn_init(ctypes.byref(self._ctx), ctypes.byref(cfg), arr, int(max_frames), int(device)):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._c("last_error")(None).decode())
+        self.sel = list(sel) if sel is not None else list(range(self.first, self.first + self.channels))
+
+    def reset(self):
+        raise IfFirError("if_fir_turn_t carries no state: there is no reset")
+
+    def set_output_format(self, fmt):
+        """if_fir_turn_set_output_format(): OUTPUT_F32 or OUTPUT_I16 (times 2^15, to nearest even, saturated; NaN gives 0)."""
+        self._check(self._L.if_fir_turn_set_output_format(self._ctx, int(fmt)))
+        self._o16 = (int(fmt) == OUTPUT_I16)
+
+    def process(self, data, pitch=None, frames=None):
+        """if_fir_turn_process(): host arrays.  TO_STREAMS: a (frames, bins) array in (complex64 / interleaved float32, or int16
+        pairs after set_input_format(INPUT_I16)), a (channels, pitch, 2) float32 or int16 array out (pitch: default frames), of
+        which [:, :frames] is written and the rest is zero.  TO_FRAMES: a (channels, pitch) array of elements in, of which the
+        first `frames` (default: pitch) of every row are used, a (frames, bins, 2) array out."""
+        x, n = self._host_input(data)
+        odt = np.int16 if self._o16 else np.float32
+        if self.direction == TURN_TO_FRAMES:
+            if n % self.channels:
+                raise IfFirError("if_fir_turn_process: %d elements are not %d rows" % (n, self.channels))
+            p = n // self.channels
+            f = p if frames is None else int(frames)
+            out = np.zeros((max(f, 0), self.bins, 2), dtype=odt)
+        else:
+            if n % self.bins:
+                raise IfFirError("if_fir_turn_process: %d elements are not whole frames of %d bins" % (n, self.bins))
+            f = n // self.bins
+            p = f if pitch is None else int(pitch)
+            out = np.zeros((self.channels, p, 2), dtype=odt)
+        dummy = np.zeros(2, dtype=np.float32)
+        self._check(self._L.if_fir_turn_process(self._ctx, ctypes.c_void_p(x.ctypes.data if x.size else dummy.ctypes.data),
+                                                ctypes.c_void_p(out.ctypes.data if out.size else dummy.ctypes.data), f, p))
+        return out
+
+    def process_device(self, dev_in, dev_out, frames, pitch=None):
+        """if_fir_turn_process_device(): raw device pointers (ints), asynchronous; pitch in elements (default: frames)."""
+        self._check(self._L.if_fir_turn_process_device(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
+                                                       int(frames), int(frames if pitch is None else pitch)))
+
+    def debug_config(self, grid_limit=0):
+        """if_fir_debug_turn_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
+        launcher's choice)."""
+        if not self._dev:
+            raise IfFirError("if_fir_debug_turn_config is in the development library only: construct with dev=True")
+        self._check(self._L.if_fir_debug_turn_config(self._ctx, int(grid_limit)))
 
 
 def debug_fft_tables(taps, decimation, complex_taps=False, nco_delta=0):
