@@ -115,6 +115,12 @@ uint8_t if_fir_debug_duc_config(if_fir_duc_t *pCtx, uint32_t ulGridLimit, uint32
 /* power-spectrum estimator (if_fir_psd_t): the plan of the next call of ullSamples samples at the current stream position:
  * pullPlan[0..3] = segments summed, chunks summed, frames emitted, samples carried after the call (nothing runs) */
 uint8_t if_fir_debug_psd_plan(const if_fir_psd_t *pCtx, uint64_t ullSamples, uint64_t *pullPlan);
+/* power-spectrum estimator: ulGridLimit as if_fir_debug_resamp_config, for the chunk kernel (one workgroup then sums several
+ * chunks; the frame and carry kernels have no stride loop); an ullPosition other than UINT64_MAX sets the stream position (the
+ * index of the next call's first sample) with nothing carried and the open frame's accumulator at +0.  It must be the first
+ * sample of a chunk: ullPosition mod H == 0 and ((ullPosition / H) mod K) mod 8 == 0; any other is refused with a message and
+ * the context is unchanged */
+uint8_t if_fir_debug_psd_config(if_fir_psd_t *pCtx, uint32_t ulGridLimit, uint64_t ullPosition);
 /* arbitrary-ratio resampler (if_fir_arb_t): ulGridLimit and *pulTileOutputs as if_fir_debug_resamp_config; an ullPosition other
  * than UINT64_MAX, on a freshly reset context, sets c = ullPosition and tau = c * 2^32 + ullTimeOffset (ullTimeOffset < 2^34) */
 uint8_t if_fir_debug_arb_config(if_fir_arb_t *pCtx, uint32_t ulGridLimit, uint32_t *pulTileOutputs, uint64_t ullPosition,

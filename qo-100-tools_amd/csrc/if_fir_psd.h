@@ -27,6 +27,7 @@ struct PsdArgs
     PsdPlan plan;            // psd_plan(position, carried, n)
     float scale;             // 1 / (K sum w^2)
     double ref_power;
+    int grid_limit;          // > 0: at most this many workgroups of the chunk kernel (development hook)
     int device;
     hipStream_t stream;
 };

@@ -145,8 +145,8 @@ static hipError_t launch_chunks(const PsdArgs &a)
     if (e != hipSuccess)
         return e;
     // a grid-stride loop over the chunks; the twiddles are staged once per workgroup, 160 KiB of LDS hold 160 / (16 N / 1024) of them
-    // (the caller launches only with chunks > 0, and there is no grid limit: at most one workgroup per chunk)
-    const unsigned groups = stream_persistent_groups(cus, N >= 4096 ? 2 : N >= 2048 ? 4 : 8, (int64_t)a.plan.chunks, 0);
+    // (the caller launches only with chunks > 0: at most one workgroup per chunk; the grid limit is 0 outside the development hook)
+    const unsigned groups = stream_persistent_groups(cus, N >= 4096 ? 2 : N >= 2048 ? 4 : 8, (int64_t)a.plan.chunks, a.grid_limit);
     hipLaunchKernelGGL((psd_chunk_kernel<N, I16>), dim3(groups), dim3(PSD_THREADS), lds, a.stream, a.in, a.carry, a.window,
                        a.twiddle, a.bin_pos, a.work, a.H, a.K, a.bins, a.plan.chunk0, (uint32_t)a.plan.chunks, a.n, a.carried);
     return hipGetLastError();

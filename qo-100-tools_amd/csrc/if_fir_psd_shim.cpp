@@ -41,6 +41,7 @@ struct if_fir_psd : if_fir::StreamCtx
     void *d_stage_in;         // if_fir_psd_process: staging, allocated by its first call (device-pointer users never pay for it)
     uint16_t *d_stage_codes;
     float *d_stage_power;
+    int grid_limit;           // development hook
 };
 
 using if_fir::set_err;
@@ -261,6 +262,7 @@ static uint8_t run_device(if_fir_psd *c, const void *in, uint16_t *codes, float 
     a.plan = plan;
     a.scale = c->scale;
     a.ref_power = c->ref_power;
+    a.grid_limit = c->grid_limit;
     a.device = c->device;
     a.stream = c->stream;
     HIP_TRY(c, if_fir::launch_psd(a));
@@ -335,6 +337,32 @@ IF_FIR_API uint8_t if_fir_debug_psd_plan(const if_fir_psd_t *pCtx, uint64_t ullS
     pullPlan[1] = plan.chunks;
     pullPlan[2] = plan.frames;
     pullPlan[3] = plan.carry;
+    return 1;
+}
+
+IF_FIR_API uint8_t if_fir_debug_psd_config(if_fir_psd_t *pCtx, uint32_t ulGridLimit, uint64_t ullPosition)
+{
+    if (!pCtx)
+        return 0;
+    if (ullPosition != UINT64_MAX)
+    {
+        // only where psd_plan accepts (position, carried = 0): on a segment's first sample, and that segment the first of a chunk
+        const uint64_t H = (uint64_t)pCtx->H, K = (uint64_t)pCtx->K;
+        if (ullPosition % H || ((ullPosition / H) % K) % if_fir::PSD_CHUNK)
+        {
+            set_err(pCtx->err, "if_fir_debug_psd_config: position %llu is not the first sample of a chunk (hop %llu, %llu segments per frame)",
+                    (unsigned long long)ullPosition, (unsigned long long)H, (unsigned long long)K);
+            return 0;
+        }
+        // the open frame's accumulator starts from +0 at the new position, whichever buffer the next call reads
+        HIP_TRY(pCtx, hipSetDevice(pCtx->device));
+        for (int i = 0; i < 2; i++)
+            HIP_TRY(pCtx, hipMemsetAsync(pCtx->d_acc[i], 0, (size_t)pCtx->bins * sizeof(float), pCtx->stream));
+        HIP_TRY(pCtx, hipStreamSynchronize(pCtx->stream));
+        pCtx->st.position = ullPosition;
+        pCtx->st.carried = 0;
+    }
+    pCtx->grid_limit = if_fir::stream_ctx_grid_limit(ulGridLimit);
     return 1;
 }
 #endif

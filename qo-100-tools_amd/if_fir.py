@@ -78,7 +78,7 @@ DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_ta
                "if_fir_debug_bank_plan", "if_fir_debug_bank_tail", "if_fir_debug_fft_schedule",
                "if_fir_mc_debug_plan", "if_fir_debug_queue_faults",
                "if_fir_debug_interp_config", "if_fir_debug_interp_seek", "if_fir_debug_interp_tables", "if_fir_debug_interp_plan",
-               "if_fir_debug_resamp_config", "if_fir_debug_psd_plan",
+               "if_fir_debug_resamp_config", "if_fir_debug_psd_plan", "if_fir_debug_psd_config",
                "if_fir_debug_combiner_config", "if_fir_debug_combiner_seek", "if_fir_debug_combiner_tables",
                "if_fir_debug_ddc_config", "if_fir_debug_duc_config", "if_fir_debug_arb_config",
                "if_fir_debug_pfb_config", "if_fir_debug_synth_config", "if_fir_debug_synth_workspace",
@@ -417,6 +417,8 @@ def _load(path, dev):
         L.if_fir_debug_combiner_tables.restype = u32
         L.if_fir_debug_psd_plan.argtypes = [vp, u64, ctypes.POINTER(u64)]
         L.if_fir_debug_psd_plan.restype = u8
+        L.if_fir_debug_psd_config.argtypes = [vp, u32, u64]
+        L.if_fir_debug_psd_config.restype = u8
         L.if_fir_debug_resamp_config.argtypes = [vp, u32, ctypes.POINTER(u32)]
         L.if_fir_debug_resamp_config.restype = u8
         L.if_fir_debug_ddc_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
@@ -1178,6 +1180,7 @@ class IfFirPsd(_StreamCtx):
     (docs/SPEC.md §8).  Methods mirror the C entry points; how many frames a call emits depends on the stream position
     (frame_count)."""
     _PREFIX = "if_fir_psd_"
+    NO_POSITION = (1 << 64) - 1
 
     def __init__(self, size, hop, segments, first_bin, bins, ref_power=1.0, window=None, input_format=INPUT_F32,
                  max_samples=1 << 20, device=0, dev=False):
@@ -1233,6 +1236,15 @@ class IfFirPsd(_StreamCtx):
         out = (ctypes.c_uint64 * 4)()
         self._check(self._L.if_fir_debug_psd_plan(self._ctx, int(samples), out))
         return tuple(int(v) for v in out)
+
+    def debug_config(self, grid_limit=0, position=None):
+        """if_fir_debug_psd_config() (development library: construct with dev=True): at most grid_limit workgroups of the chunk
+        kernel (0 = the launcher's choice); position (optional) = the stream position of the next call's first sample, the first
+        sample of a chunk, with nothing carried and the open frame's accumulator at +0."""
+        if not self._dev:
+            raise IfFirError("if_fir_debug_psd_config is in the development library only: construct with dev=True")
+        self._check(self._L.if_fir_debug_psd_config(self._ctx, int(grid_limit),
+                                                    self.NO_POSITION if position is None else int(position)))
 
 
 class IfFirPfb(_StreamCtx):

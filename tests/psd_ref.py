@@ -147,3 +147,58 @@ def matrix_signal(base, N, i16):
         return xi, xi.astype(np.float32) * np.float32(2.0 ** -15)
     x = x.astype(np.float32)
     return x, x
+
+
+# ---- long averages (tests/test_psd_long_gpu.py, measured on the host by tests/test_psd_host.py) -----------------------------
+# (N, H, K): ceil(K / 8) from 126 to 8192 accumulator additions per frame
+LONG = ((256, 1, 65535), (512, 2, 8200), (1024, 1, 4097), (1024, 385, 1003), (2048, 1, 8195), (4096, 1, 8209))
+# the complex64 implementation's worst error over LONG x {float32, int16} x {Hann, asymmetric}, at (256, 1, 65535, int16, Hann)
+C64_WORST_LONG = 3.226e-6
+
+
+def eps_of(K):
+    """SPEC §8's tolerance for a frame of K segments: EPS while the accumulator takes at most the 3 additions the matrix covers;
+    beyond, every addition rounds once, by at most 2^-24 of a partial sum of non-negative terms that is at most the frame's
+    peak.  Counting all ceil(K / 8) additions leaves three units for second order."""
+    chunks = (K + CHUNK - 1) // CHUNK
+    return EPS if chunks <= 3 else EPS + chunks * 2.0 ** -24
+
+
+def long_samples(N, H, K):
+    """one whole frame, 11 segments of the next and an odd remainder"""
+    return (K + 11) * H + N + 5
+
+
+def power_f64_segments(iq, N, H, K, seg_lo, seg_hi, window=None, first_bin=None, bins=None):
+    """(bins,) float64: the sum of S over the stream's segments seg_lo .. seg_hi - 1 only, over K sum w^2: what a context whose
+    stream starts inside a frame, at segment seg_lo of it, emits for that frame (seg_hi = K)"""
+    w = (hann(N) if window is None else np.asarray(window, dtype=np.float32)).astype(np.float64)
+    x = as_c(iq)
+    assert 0 <= seg_lo < seg_hi <= segments_complete(x.size, N, H)
+    sel = bin_indices(N, -N // 2 if first_bin is None else first_bin, N if bins is None else bins)
+    seg = _segments(x, N, H, seg_hi)[seg_lo:]
+    S = np.abs(np.fft.fft(seg * w, axis=1)[:, sel]) ** 2
+    return S.sum(axis=0) / (K * np.sum(w * w))
+
+
+def chunk_order_power(chunk_sums, K, N):
+    """the frame a ones-window context of K segments makes of its float32 chunk sums ((chunks, bins), in chunk order): onto a
+    float32 accumulator that starts at +0, one addition per chunk, then one float32 product by 1 / (K N) rounded once from
+    float64 (sum w^2 = N exactly)"""
+    chunk_sums = np.asarray(chunk_sums)
+    assert chunk_sums.dtype == np.float32 and chunk_sums.shape[0] == (K + CHUNK - 1) // CHUNK
+    acc = np.zeros(chunk_sums.shape[1], dtype=np.float32)
+    for part in chunk_sums:
+        acc = acc + part
+    assert acc.dtype == np.float32
+    return acc * np.float32(1.0 / (float(K) * float(N)))
+
+
+def segment_order_sum(segment_powers):
+    """a chunk sum from its segments' float32 powers ((segments, bins), in segment order): float32 additions onto +0"""
+    segment_powers = np.asarray(segment_powers)
+    assert segment_powers.dtype == np.float32 and 1 <= segment_powers.shape[0] <= CHUNK
+    part = np.zeros(segment_powers.shape[1], dtype=np.float32)
+    for s in segment_powers:
+        part = part + s
+    return part
