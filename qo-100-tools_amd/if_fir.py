@@ -19,72 +19,6 @@ OUTPUT_F32, OUTPUT_I16 = 0, 1
 BACKEND_AUTO, BACKEND_HIP_DIRECT, BACKEND_HIP_TAPSPLIT, BACKEND_HIP_GENERIC, BACKEND_HIP_FFT = range(5)
 WINDOW_RECT, WINDOW_HAMMING, WINDOW_HANN, WINDOW_BLACKMAN = range(4)
 
-# every symbol include/if_fir.h declares (tests check the library exports all of them)
-EXPORTS = [
-    "if_bpf_design", "if_bpf_design_complex", "if_fir_init", "if_fir_init_complex", "if_fir_destroy", "if_fir_reset", "if_fir_set_backend", "if_fir_get_backend",
-    "if_fir_set_tuning", "if_fir_set_input_format", "if_fir_set_stream", "if_fir_synchronize", "if_fir_last_error", "if_fir_out_count",
-    "if_fir_process", "if_fir_process_device", "if_fir_synth_device", "if_fir_dev_alloc",
-    "if_fir_dev_free", "if_fir_dev_upload", "if_fir_dev_download", "if_fir_device_info",
-    "if_fir_set_nco", "if_fir_get_nco", "if_fir_channelizer_process_device", "if_fir_channelizer_process_device_freq", "if_fir_host_alloc", "if_fir_host_free",
-    "if_fir_power_device",
-    "if_fir_mc_owner", "if_fir_mc_unique_id", "if_fir_mc_init", "if_fir_mc_destroy", "if_fir_mc_reset",
-    "if_fir_mc_set_input_format", "if_fir_mc_process_device", "if_fir_mc_channel_ctx", "if_fir_mc_last_error",
-    "if_fir_mc_set_chunk_samples", "if_fir_mc_get_chunk_samples",
-    "if_fir_interp_init", "if_fir_interp_init_complex", "if_fir_interp_destroy", "if_fir_interp_reset", "if_fir_interp_set_backend",
-    "if_fir_interp_get_backend", "if_fir_interp_set_input_format", "if_fir_interp_set_nco", "if_fir_interp_get_nco",
-    "if_fir_interp_set_stream", "if_fir_interp_synchronize", "if_fir_interp_last_error", "if_fir_interp_out_count",
-    "if_fir_interp_process", "if_fir_interp_process_device",
-    "if_fir_resamp_init", "if_fir_resamp_init_complex", "if_fir_resamp_destroy", "if_fir_resamp_reset", "if_fir_resamp_set_input_format",
-    "if_fir_resamp_set_stream", "if_fir_resamp_synchronize", "if_fir_resamp_last_error", "if_fir_resamp_out_count",
-    "if_fir_resamp_process", "if_fir_resamp_process_device",
-    "if_fir_psd_init", "if_fir_psd_destroy", "if_fir_psd_reset", "if_fir_psd_set_input_format", "if_fir_psd_set_stream",
-    "if_fir_psd_synchronize", "if_fir_psd_last_error", "if_fir_psd_frame_count", "if_fir_psd_process", "if_fir_psd_process_device",
-    "if_fir_combiner_init", "if_fir_combiner_init_complex", "if_fir_combiner_destroy", "if_fir_combiner_reset", "if_fir_combiner_set_backend",
-    "if_fir_combiner_get_backend", "if_fir_combiner_set_input_format", "if_fir_combiner_set_centres", "if_fir_combiner_get_centres",
-    "if_fir_combiner_set_stream", "if_fir_combiner_synchronize", "if_fir_combiner_last_error", "if_fir_combiner_out_count",
-    "if_fir_combiner_process", "if_fir_combiner_process_device",
-    "if_fir_ddc_init", "if_fir_ddc_init_complex", "if_fir_ddc_destroy", "if_fir_ddc_reset", "if_fir_ddc_set_input_format",
-    "if_fir_ddc_set_nco", "if_fir_ddc_get_nco", "if_fir_ddc_set_stream", "if_fir_ddc_synchronize", "if_fir_ddc_last_error",
-    "if_fir_ddc_out_count", "if_fir_ddc_process", "if_fir_ddc_process_device",
-    "if_fir_duc_init", "if_fir_duc_init_complex", "if_fir_duc_destroy", "if_fir_duc_reset", "if_fir_duc_set_input_format",
-    "if_fir_duc_set_output_format", "if_fir_duc_set_nco", "if_fir_duc_get_nco", "if_fir_duc_set_stream", "if_fir_duc_synchronize",
-    "if_fir_duc_last_error", "if_fir_duc_out_count", "if_fir_duc_process", "if_fir_duc_process_device",
-    "if_fir_arb_init", "if_fir_arb_destroy", "if_fir_arb_reset", "if_fir_arb_set_step", "if_fir_arb_set_input_format",
-    "if_fir_arb_set_stream", "if_fir_arb_synchronize", "if_fir_arb_last_error", "if_fir_arb_out_count", "if_fir_arb_process",
-    "if_fir_arb_process_device", "if_fir_arb_step_from_rates",
-    "if_fir_pfb_init", "if_fir_pfb_destroy", "if_fir_pfb_reset", "if_fir_pfb_set_input_format", "if_fir_pfb_set_stream",
-    "if_fir_pfb_synchronize", "if_fir_pfb_last_error", "if_fir_pfb_frame_count", "if_fir_pfb_process", "if_fir_pfb_process_device",
-    "if_fir_synth_init", "if_fir_synth_destroy", "if_fir_synth_reset", "if_fir_synth_set_input_format", "if_fir_synth_set_stream",
-    "if_fir_synth_synchronize", "if_fir_synth_last_error", "if_fir_synth_sample_count", "if_fir_synth_process",
-    "if_fir_synth_process_device",
-    "if_fir_sub_init", "if_fir_sub_destroy", "if_fir_sub_reset", "if_fir_sub_set_input_format", "if_fir_sub_set_nco", "if_fir_sub_get_nco",
-    "if_fir_sub_set_stream", "if_fir_sub_synchronize", "if_fir_sub_last_error", "if_fir_sub_frame_count", "if_fir_sub_process",
-    "if_fir_sub_process_device",
-    "if_fir_subup_init", "if_fir_subup_destroy", "if_fir_subup_reset", "if_fir_subup_set_input_format", "if_fir_subup_set_nco",
-    "if_fir_subup_get_nco", "if_fir_subup_set_stream", "if_fir_subup_synchronize", "if_fir_subup_last_error", "if_fir_subup_frame_count",
-    "if_fir_subup_process", "if_fir_subup_process_device",
-    "if_fir_rpfb_init", "if_fir_rpfb_destroy", "if_fir_rpfb_reset", "if_fir_rpfb_set_input_format", "if_fir_rpfb_set_stream",
-    "if_fir_rpfb_synchronize", "if_fir_rpfb_last_error", "if_fir_rpfb_frame_count", "if_fir_rpfb_process", "if_fir_rpfb_process_device",
-    "if_fir_rsynth_init", "if_fir_rsynth_destroy", "if_fir_rsynth_reset", "if_fir_rsynth_set_input_format", "if_fir_rsynth_set_output_format",
-    "if_fir_rsynth_set_stream", "if_fir_rsynth_synchronize", "if_fir_rsynth_last_error", "if_fir_rsynth_sample_count", "if_fir_rsynth_process",
-    "if_fir_rsynth_process_device",
-    "if_fir_fpow_init", "if_fir_fpow_destroy", "if_fir_fpow_reset", "if_fir_fpow_set_input_format", "if_fir_fpow_set_stream",
-    "if_fir_fpow_synchronize", "if_fir_fpow_last_error", "if_fir_fpow_frame_count", "if_fir_fpow_process", "if_fir_fpow_process_device",
-    "if_fir_turn_init", "if_fir_turn_destroy", "if_fir_turn_set_input_format", "if_fir_turn_set_output_format", "if_fir_turn_set_stream",
-    "if_fir_turn_synchronize", "if_fir_turn_last_error", "if_fir_turn_process", "if_fir_turn_process_device",
-]
-# every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
-DEV_EXPORTS = ["if_fir_time_device", "if_fir_debug_stamps", "if_fir_debug_fft_tables", "if_fir_debug_fft_tables_odd", "if_fir_debug_fft_tables_bank",
-               "if_fir_debug_bank_plan", "if_fir_debug_bank_tail", "if_fir_debug_fft_schedule",
-               "if_fir_mc_debug_plan", "if_fir_debug_queue_faults",
-               "if_fir_debug_interp_config", "if_fir_debug_interp_seek", "if_fir_debug_interp_tables", "if_fir_debug_interp_plan",
-               "if_fir_debug_resamp_config", "if_fir_debug_psd_plan", "if_fir_debug_psd_config",
-               "if_fir_debug_combiner_config", "if_fir_debug_combiner_seek", "if_fir_debug_combiner_tables",
-               "if_fir_debug_ddc_config", "if_fir_debug_duc_config", "if_fir_debug_arb_config",
-               "if_fir_debug_pfb_config", "if_fir_debug_synth_config", "if_fir_debug_synth_workspace",
-               "if_fir_debug_sub_config", "if_fir_debug_subup_config", "if_fir_debug_rpfb_config",
-               "if_fir_debug_rsynth_config", "if_fir_debug_rsynth_workspace", "if_fir_debug_fpow_config",
-               "if_fir_debug_turn_config"]
 MC_ID_BYTES = 128
 
 
@@ -140,6 +74,134 @@ class IfFirError(RuntimeError):
     pass
 
 
+# The C ABI, written down once: name -> (restype, [argtypes]) of every symbol include/if_fir.h declares (ABI) and of every symbol
+# include/if_fir_debug.h declares (DEV_ABI).  _load() applies them, EXPORTS and DEV_EXPORTS are their keys, and
+# tests/test_binding_host.py holds every entry against its prototype in the header.  A new family adds its name to _FAMILIES and
+# one _declare() per table below.
+_U8, _U32, _U64, _I32, _F64, _VP, _STR = (ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_double,
+                                          ctypes.c_void_p, ctypes.c_char_p)
+_U8P, _U16P, _U32P, _U64P, _I32P, _I64P, _F32P, _F64P, _VPP = (ctypes.POINTER(t) for t in (
+    ctypes.c_uint8, ctypes.c_uint16, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double,
+    ctypes.c_void_p))
+# the signatures that recur
+_DESIGN = (_U8, [_F32P, _U32, _F64, _F64, _U32])
+_INIT_TAPS = (_U8, [_VPP, _F32P, _U32, _U32, _U64, _I32])       # (&ctx, taps, tap count, ratio, max_samples, device)
+_DESTROY = (None, [_VP])
+_STATUS = (_U8, [_VP])
+_LAST_ERROR = (_STR, [_VP])
+_SET_U32 = (_U8, [_VP, _U32])
+_GET_U32 = (_U32, [_VP])
+_SET_U64 = (_U8, [_VP, _U64])
+_SET_PTR = (_U8, [_VP, _VP])
+_SET_F64 = (_U8, [_VP, _F64])
+_F64_ARRAY = (_U8, [_VP, _F64P])                                # one double out, or one per channel / bin in or out
+_COUNT = (_U64, [_VP, _U64])
+_ALLOC = (_U8, [_VP, _VPP, _U64])
+_COPY = (_U8, [_VP, _VP, _VP, _U64])
+_PROCESS_F32 = (_U8, [_VP, _VP, _F32P, _U64, _U64P])            # host: (ctx, in, float out, count, &emitted)
+_PROCESS_ANY = (_U8, [_VP, _VP, _VP, _U64, _U64P])              # (ctx, in, out, count, &emitted): every counted process_device
+_PROCESS_CODES = (_U8, [_VP, _VP, _U64, _U16P, _F32P, _U32P])   # host: (ctx, in, count, codes, powers, &frames)
+_PROCESS_CODES_DEVICE = (_U8, [_VP, _VP, _U64, _VP, _VP, _U32P])
+_TILE_CONFIG = (_U8, [_VP, _U32, _U32P, _U64])                  # (ctx, grid limit, &tile, position)
+_POSITION_CONFIG = (_U8, [_VP, _U32, _U64])                     # (ctx, grid limit, position)
+_QUERY_U64 = (_U8, [_VP, _U64, _U64P])                          # (ctx, a count or a budget, what it comes to)
+_FFT_TABLES = (_U32, [_F32P, _U32, _U32, _U32, _U32, _F32P, _U32])
+
+ABI = {
+    "if_bpf_design": _DESIGN, "if_bpf_design_complex": _DESIGN,
+    "if_fir_init": _INIT_TAPS, "if_fir_init_complex": _INIT_TAPS, "if_fir_destroy": _DESTROY, "if_fir_reset": _STATUS,
+    "if_fir_set_backend": _SET_U32, "if_fir_get_backend": _GET_U32, "if_fir_set_tuning": _SET_U32, "if_fir_set_input_format": _SET_U32,
+    "if_fir_set_stream": _SET_PTR, "if_fir_synchronize": _STATUS, "if_fir_last_error": _LAST_ERROR, "if_fir_out_count": _COUNT,
+    "if_fir_process": (_U8, [_VP, _F32P, _F32P, _U64, _U64P]), "if_fir_process_device": _PROCESS_ANY,
+    "if_fir_synth_device": (_U8, [_VP, _VP, _U64, _U64, _U32]),
+    "if_fir_dev_alloc": _ALLOC, "if_fir_dev_free": _SET_PTR, "if_fir_dev_upload": _COPY, "if_fir_dev_download": _COPY,
+    "if_fir_device_info": (_U8, [_VP, _STR, _U32]), "if_fir_set_nco": _SET_F64, "if_fir_get_nco": _F64_ARRAY,
+    "if_fir_channelizer_process_device": (_U8, [_VP, _U32, _U32P, _VP, _VPP, _U64, _U64P]),
+    "if_fir_channelizer_process_device_freq": (_U8, [_VP, _U32, _F64P, _VP, _VPP, _U64, _U64P]),
+    "if_fir_host_alloc": _ALLOC, "if_fir_host_free": _SET_PTR, "if_fir_power_device": (_U8, [_VP, _VP, _U64, _F64P]),
+    "if_fir_mc_owner": (_U32, [_U32, _U32]), "if_fir_mc_unique_id": (_U8, [_U8P]),
+    "if_fir_mc_init": (_U8, [_VPP, _U32, _F32P, _U32, _U32, _U64, _I32, _U32, _U32, _U8P]),
+    "if_fir_mc_destroy": _DESTROY, "if_fir_mc_reset": _STATUS, "if_fir_mc_set_input_format": _SET_U32,
+    "if_fir_mc_process_device": (_U8, [_VP, _VPP, _VPP, _U64, _U64P]), "if_fir_mc_channel_ctx": (_VP, [_VP, _U32]),
+    "if_fir_mc_last_error": _LAST_ERROR, "if_fir_mc_set_chunk_samples": _SET_U64,
+    "if_fir_mc_get_chunk_samples": (_U8, [_VP, _U64P, _U64P]),
+}
+DEV_ABI = {
+    "if_fir_time_device": (_U8, [_VP, _VP, _VP, _U64, _U32, _U32, _F32P]), "if_fir_debug_stamps": (_U32, [_VP, _U64P, _U32]),
+    "if_fir_debug_fft_tables": _FFT_TABLES, "if_fir_debug_fft_tables_odd": _FFT_TABLES, "if_fir_debug_fft_tables_bank": _FFT_TABLES,
+    "if_fir_debug_bank_plan": (_U8, [_U32P, _U32, _U32P]), "if_fir_debug_bank_tail": (_U32, [_U32, _U32]),
+    "if_fir_debug_fft_schedule": (_U8, [_U64, _U32, _U32, _I64P]),
+    "if_fir_mc_debug_plan": (_U32, [_U32, _U32, _U32, _U64, _U32, _U32, _U32, _U64, _U64, _U64P, _U32]),
+    "if_fir_debug_queue_faults": (_U8, [_VP, _U32P]),
+}
+
+
+def _declare(table, stem, **calls):
+    """table[stem + call] = (restype, [argtypes]) for every call=(restype, [argtypes]) given"""
+    table.update((stem + call, signature) for call, signature in calls.items())
+
+
+# the streaming families (_StreamCtx): the calls every one declares alike, then, per family, its own product calls
+# (if_fir_<family>_<call>) and its development hooks (if_fir_debug_<family>_<call>)
+_FAMILIES = ("interp", "resamp", "psd", "combiner", "ddc", "duc", "arb", "pfb", "synth", "sub", "subup", "rpfb", "rsynth", "fpow", "turn")
+_STATELESS = ("turn",)   # the corner turn carries no state: it has no reset
+for _family in _FAMILIES:
+    _declare(ABI, "if_fir_%s_" % _family, destroy=_DESTROY, synchronize=_STATUS, set_input_format=_SET_U32, set_stream=_SET_PTR,
+             last_error=_LAST_ERROR)
+    if _family not in _STATELESS:
+        _declare(ABI, "if_fir_%s_" % _family, reset=_STATUS)
+_declare(ABI, "if_fir_interp_", init=_INIT_TAPS, init_complex=_INIT_TAPS, set_backend=_SET_U32, get_backend=_GET_U32, set_nco=_SET_F64,
+         get_nco=_F64_ARRAY, out_count=_COUNT, process=_PROCESS_F32, process_device=_PROCESS_ANY)
+_declare(DEV_ABI, "if_fir_debug_interp_", config=(_U8, [_VP, _U32, _U32]), seek=_SET_U64, tables=(_U32, [_F32P, _U32, _U32, _F32P, _U32]),
+         plan=(_U8, [_U32, _U32, _U32P, _U32P, _U32P]))
+_INIT_RESAMP = (_U8, [_VPP, _F32P, _U32, _U32, _U32, _U64, _I32])
+_declare(ABI, "if_fir_resamp_", init=_INIT_RESAMP, init_complex=_INIT_RESAMP, out_count=_COUNT, process=_PROCESS_F32,
+         process_device=_PROCESS_ANY)
+_declare(DEV_ABI, "if_fir_debug_resamp_", config=(_U8, [_VP, _U32, _U32P]))
+_declare(ABI, "if_fir_psd_", init=(_U8, [_VPP, ctypes.POINTER(PsdConfig), _F32P, _U64, _I32]), frame_count=_COUNT,
+         process=_PROCESS_CODES, process_device=_PROCESS_CODES_DEVICE)
+_declare(DEV_ABI, "if_fir_debug_psd_", plan=_QUERY_U64, config=_POSITION_CONFIG)
+_INIT_COMBINER = (_U8, [_VPP, _F32P, _U32, _U32, _U32, _F64P, _U64, _I32])
+_declare(ABI, "if_fir_combiner_", init=_INIT_COMBINER, init_complex=_INIT_COMBINER, set_backend=_SET_U32, get_backend=_GET_U32,
+         set_centres=_F64_ARRAY, get_centres=_F64_ARRAY, out_count=_COUNT, process=(_U8, [_VP, _VPP, _F32P, _U64, _U64P]),
+         process_device=(_U8, [_VP, _VPP, _VP, _U64, _U64P]))
+_declare(DEV_ABI, "if_fir_debug_combiner_", config=_SET_U32, seek=_SET_U64,
+         tables=(_U32, [_F32P, _U32, _U32, _F64, _U32P, _I32P, _F32P, _U32]))
+_declare(ABI, "if_fir_ddc_", init=_INIT_TAPS, init_complex=_INIT_TAPS, set_nco=_SET_F64, get_nco=_F64_ARRAY, out_count=_COUNT,
+         process=_PROCESS_F32, process_device=_PROCESS_ANY)
+_declare(DEV_ABI, "if_fir_debug_ddc_", config=_TILE_CONFIG)
+_declare(ABI, "if_fir_duc_", init=_INIT_TAPS, init_complex=_INIT_TAPS, set_output_format=_SET_U32, set_nco=_SET_F64, get_nco=_F64_ARRAY,
+         out_count=_COUNT, process=_PROCESS_ANY, process_device=_PROCESS_ANY)
+_declare(DEV_ABI, "if_fir_debug_duc_", config=_TILE_CONFIG)
+_declare(ABI, "if_fir_arb_", init=(_U8, [_VPP, _F32P, _U32, _U32, _U64, _U64, _I32]), set_step=_SET_U64, out_count=_COUNT,
+         process=_PROCESS_F32, process_device=_PROCESS_ANY, step_from_rates=(_U64, [_F64, _F64]))
+_declare(DEV_ABI, "if_fir_debug_arb_", config=(_U8, [_VP, _U32, _U32P, _U64, _U64]))
+for _family, _config in (("pfb", PfbConfig), ("rpfb", RpfbConfig)):
+    _declare(ABI, "if_fir_%s_" % _family, init=(_U8, [_VPP, ctypes.POINTER(_config), _F32P, _U32, _U64, _I32]), frame_count=_COUNT,
+             process=_PROCESS_F32, process_device=_PROCESS_ANY)
+    _declare(DEV_ABI, "if_fir_debug_%s_" % _family, config=_TILE_CONFIG)
+_declare(ABI, "if_fir_synth_", init=(_U8, [_VPP, ctypes.POINTER(SynthConfig), _F32P, _U32, _U64, _I32]), sample_count=_COUNT,
+         process=_PROCESS_F32, process_device=_PROCESS_ANY)
+_declare(DEV_ABI, "if_fir_debug_synth_", config=(_U8, [_VP, _U32, _U32, _U32P, _U64]), workspace=_QUERY_U64)
+_declare(ABI, "if_fir_rsynth_", init=(_U8, [_VPP, ctypes.POINTER(RsynthConfig), _F32P, _U32, _U64, _I32]), set_output_format=_SET_U32,
+         sample_count=_COUNT, process=_PROCESS_ANY, process_device=_PROCESS_ANY)
+_declare(DEV_ABI, "if_fir_debug_rsynth_", config=_POSITION_CONFIG, workspace=_QUERY_U64)
+for _family, _config in (("sub", SubConfig), ("subup", SubUpConfig)):
+    _declare(ABI, "if_fir_%s_" % _family, init=(_U8, [_VPP, ctypes.POINTER(_config), _F32P, _U64, _I32]), set_nco=_F64_ARRAY,
+             get_nco=_F64_ARRAY, frame_count=_COUNT, process=_PROCESS_F32, process_device=_PROCESS_ANY)
+    _declare(DEV_ABI, "if_fir_debug_%s_" % _family, config=_TILE_CONFIG)
+del _family, _config
+_declare(ABI, "if_fir_fpow_", init=(_U8, [_VPP, ctypes.POINTER(FpowConfig), _U64, _I32]), frame_count=_COUNT, process=_PROCESS_CODES,
+         process_device=_PROCESS_CODES_DEVICE)
+_declare(DEV_ABI, "if_fir_debug_fpow_", config=_POSITION_CONFIG)
+_TURN = (_U8, [_VP, _VP, _VP, _U64, _U64])
+_declare(ABI, "if_fir_turn_", init=(_U8, [_VPP, ctypes.POINTER(TurnConfig), _U32P, _U64, _I32]), set_output_format=_SET_U32,
+         process=_TURN, process_device=_TURN)
+_declare(DEV_ABI, "if_fir_debug_turn_", config=_SET_U32)
+
+EXPORTS = list(ABI)           # every symbol include/if_fir.h declares (tests check the library exports all of them)
+DEV_EXPORTS = list(DEV_ABI)   # every symbol include/if_fir_debug.h declares: exported by libif_fir_dev.so only
+
 _libs = {}
 
 
@@ -154,305 +216,31 @@ def dev_lib():
 
 
 def _load(path, dev):
+    """Open a build of the library and give every symbol of ABI (and, for a development build, of DEV_ABI) its signature."""
     if path in _libs:
         return _libs[path]
     if not os.path.exists(path):
         raise IfFirError("%s is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`"
                          % (os.path.basename(path), path))
     L = ctypes.CDLL(path)
-    u8, u32, u64, i32, vp = ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_void_p
-    f32p = ctypes.POINTER(ctypes.c_float)
-    L.if_bpf_design.argtypes = [f32p, u32, ctypes.c_double, ctypes.c_double, u32]
-    L.if_bpf_design.restype = u8
-    L.if_fir_init.argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u64, i32]
-    L.if_fir_init.restype = u8
-    L.if_fir_init_complex.argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u64, i32]
-    L.if_fir_init_complex.restype = u8
-    L.if_bpf_design_complex.argtypes = [f32p, u32, ctypes.c_double, ctypes.c_double, u32]
-    L.if_bpf_design_complex.restype = u8
-    L.if_fir_destroy.argtypes = [vp]
-    L.if_fir_destroy.restype = None
-    L.if_fir_reset.argtypes = [vp]
-    L.if_fir_reset.restype = u8
-    L.if_fir_set_backend.argtypes = [vp, u32]
-    L.if_fir_set_backend.restype = u8
-    L.if_fir_get_backend.argtypes = [vp]
-    L.if_fir_get_backend.restype = u32
-    L.if_fir_set_input_format.argtypes = [vp, u32]
-    L.if_fir_set_input_format.restype = u8
-    L.if_fir_set_tuning.argtypes = [vp, u32]
-    L.if_fir_set_tuning.restype = u8
-    L.if_fir_set_stream.argtypes = [vp, vp]
-    L.if_fir_set_stream.restype = u8
-    L.if_fir_synchronize.argtypes = [vp]
-    L.if_fir_synchronize.restype = u8
-    L.if_fir_last_error.argtypes = [vp]
-    L.if_fir_last_error.restype = ctypes.c_char_p
-    L.if_fir_out_count.argtypes = [vp, u64]
-    L.if_fir_out_count.restype = u64
-    L.if_fir_process.argtypes = [vp, f32p, f32p, u64, ctypes.POINTER(u64)]
-    L.if_fir_process.restype = u8
-    L.if_fir_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
-    L.if_fir_process_device.restype = u8
-    L.if_fir_synth_device.argtypes = [vp, vp, u64, u64, u32]
-    L.if_fir_synth_device.restype = u8
-    L.if_fir_dev_alloc.argtypes = [vp, ctypes.POINTER(vp), u64]
-    L.if_fir_dev_alloc.restype = u8
-    L.if_fir_dev_free.argtypes = [vp, vp]
-    L.if_fir_dev_free.restype = u8
-    L.if_fir_dev_upload.argtypes = [vp, vp, vp, u64]
-    L.if_fir_dev_upload.restype = u8
-    L.if_fir_dev_download.argtypes = [vp, vp, vp, u64]
-    L.if_fir_dev_download.restype = u8
-    L.if_fir_device_info.argtypes = [vp, ctypes.c_char_p, u32]
-    L.if_fir_device_info.restype = u8
-    L.if_fir_set_nco.argtypes = [vp, ctypes.c_double]
-    L.if_fir_set_nco.restype = u8
-    L.if_fir_get_nco.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
-    L.if_fir_get_nco.restype = u8
-    L.if_fir_channelizer_process_device.argtypes = [vp, u32, ctypes.POINTER(u32), vp, ctypes.POINTER(vp), u64,
-                                                    ctypes.POINTER(u64)]
-    L.if_fir_channelizer_process_device.restype = u8
-    L.if_fir_channelizer_process_device_freq.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_double), vp, ctypes.POINTER(vp), u64,
-                                                         ctypes.POINTER(u64)]
-    L.if_fir_channelizer_process_device_freq.restype = u8
-    L.if_fir_host_alloc.argtypes = [vp, ctypes.POINTER(vp), u64]
-    L.if_fir_host_alloc.restype = u8
-    L.if_fir_host_free.argtypes = [vp, vp]
-    L.if_fir_host_free.restype = u8
-    L.if_fir_power_device.argtypes = [vp, vp, u64, ctypes.POINTER(ctypes.c_double)]
-    L.if_fir_power_device.restype = u8
-    u8p = ctypes.POINTER(ctypes.c_uint8)
-    L.if_fir_mc_owner.argtypes = [u32, u32]
-    L.if_fir_mc_owner.restype = u32
-    L.if_fir_mc_unique_id.argtypes = [u8p]
-    L.if_fir_mc_unique_id.restype = u8
-    L.if_fir_mc_init.argtypes = [ctypes.POINTER(vp), u32, f32p, u32, u32, u64, i32, u32, u32, u8p]
-    L.if_fir_mc_init.restype = u8
-    L.if_fir_mc_destroy.argtypes = [vp]
-    L.if_fir_mc_destroy.restype = None
-    L.if_fir_mc_reset.argtypes = [vp]
-    L.if_fir_mc_reset.restype = u8
-    L.if_fir_mc_set_input_format.argtypes = [vp, u32]
-    L.if_fir_mc_set_input_format.restype = u8
-    L.if_fir_mc_process_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), u64, ctypes.POINTER(u64)]
-    L.if_fir_mc_process_device.restype = u8
-    L.if_fir_mc_channel_ctx.argtypes = [vp, u32]
-    L.if_fir_mc_channel_ctx.restype = vp
-    L.if_fir_mc_last_error.argtypes = [vp]
-    L.if_fir_mc_last_error.restype = ctypes.c_char_p
-    L.if_fir_mc_set_chunk_samples.argtypes = [vp, u64]
-    L.if_fir_mc_set_chunk_samples.restype = u8
-    L.if_fir_mc_get_chunk_samples.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
-    L.if_fir_mc_get_chunk_samples.restype = u8
-    # the streaming contexts (_StreamCtx): what the families declare alike, then what each has of its own
-    for prefix in ("if_fir_interp_", "if_fir_resamp_", "if_fir_psd_", "if_fir_combiner_", "if_fir_ddc_", "if_fir_duc_", "if_fir_arb_",
-                   "if_fir_pfb_", "if_fir_synth_", "if_fir_sub_", "if_fir_subup_", "if_fir_rpfb_", "if_fir_rsynth_", "if_fir_fpow_"):
-        for name, args, res in (("destroy", [vp], None), ("reset", [vp], u8), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
-                                ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p)):
-            getattr(L, prefix + name).argtypes = args
-            getattr(L, prefix + name).restype = res
-    for prefix, init_args in (("if_fir_interp_", [ctypes.POINTER(vp), f32p, u32, u32, u64, i32]),
-                              ("if_fir_resamp_", [ctypes.POINTER(vp), f32p, u32, u32, u32, u64, i32]),
-                              ("if_fir_ddc_", [ctypes.POINTER(vp), f32p, u32, u32, u64, i32])):
-        for name, args, res in (("init", init_args, u8), ("init_complex", init_args, u8), ("out_count", [vp, u64], u64),
-                                ("process", [vp, vp, f32p, u64, ctypes.POINTER(u64)], u8),
-                                ("process_device", [vp, vp, vp, u64, ctypes.POINTER(u64)], u8)):
-            getattr(L, prefix + name).argtypes = args
-            getattr(L, prefix + name).restype = res
-    L.if_fir_interp_set_backend.argtypes = [vp, u32]
-    L.if_fir_interp_set_backend.restype = u8
-    L.if_fir_interp_get_backend.argtypes = [vp]
-    L.if_fir_interp_get_backend.restype = u32
-    L.if_fir_interp_set_nco.argtypes = [vp, ctypes.c_double]
-    L.if_fir_interp_set_nco.restype = u8
-    L.if_fir_interp_get_nco.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
-    L.if_fir_interp_get_nco.restype = u8
-    L.if_fir_ddc_set_nco.argtypes = [vp, ctypes.c_double]
-    L.if_fir_ddc_set_nco.restype = u8
-    L.if_fir_ddc_get_nco.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
-    L.if_fir_ddc_get_nco.restype = u8
-    for name, args, res in (("init", [ctypes.POINTER(vp), f32p, u32, u32, u64, i32], u8),
-                            ("init_complex", [ctypes.POINTER(vp), f32p, u32, u32, u64, i32], u8), ("out_count", [vp, u64], u64),
-                            ("process", [vp, vp, vp, u64, ctypes.POINTER(u64)], u8),
-                            ("process_device", [vp, vp, vp, u64, ctypes.POINTER(u64)], u8), ("set_output_format", [vp, u32], u8),
-                            ("set_nco", [vp, ctypes.c_double], u8), ("get_nco", [vp, ctypes.POINTER(ctypes.c_double)], u8)):
-        getattr(L, "if_fir_duc_" + name).argtypes = args
-        getattr(L, "if_fir_duc_" + name).restype = res
-    for name, args, res in (("init", [ctypes.POINTER(vp), f32p, u32, u32, u64, u64, i32], u8), ("set_step", [vp, u64], u8),
-                            ("out_count", [vp, u64], u64), ("process", [vp, vp, f32p, u64, ctypes.POINTER(u64)], u8),
-                            ("process_device", [vp, vp, vp, u64, ctypes.POINTER(u64)], u8),
-                            ("step_from_rates", [ctypes.c_double, ctypes.c_double], u64)):
-        getattr(L, "if_fir_arb_" + name).argtypes = args
-        getattr(L, "if_fir_arb_" + name).restype = res
-    f64p = ctypes.POINTER(ctypes.c_double)
-    for name in ("init", "init_complex"):
-        getattr(L, "if_fir_combiner_" + name).argtypes = [ctypes.POINTER(vp), f32p, u32, u32, u32, f64p, u64, i32]
-        getattr(L, "if_fir_combiner_" + name).restype = u8
-    L.if_fir_combiner_set_backend.argtypes = [vp, u32]
-    L.if_fir_combiner_set_backend.restype = u8
-    L.if_fir_combiner_get_backend.argtypes = [vp]
-    L.if_fir_combiner_get_backend.restype = u32
-    L.if_fir_combiner_set_centres.argtypes = [vp, f64p]
-    L.if_fir_combiner_set_centres.restype = u8
-    L.if_fir_combiner_get_centres.argtypes = [vp, f64p]
-    L.if_fir_combiner_get_centres.restype = u8
-    L.if_fir_combiner_out_count.argtypes = [vp, u64]
-    L.if_fir_combiner_out_count.restype = u64
-    L.if_fir_combiner_process.argtypes = [vp, ctypes.POINTER(vp), f32p, u64, ctypes.POINTER(u64)]
-    L.if_fir_combiner_process.restype = u8
-    L.if_fir_combiner_process_device.argtypes = [vp, ctypes.POINTER(vp), vp, u64, ctypes.POINTER(u64)]
-    L.if_fir_combiner_process_device.restype = u8
-    u16p = ctypes.POINTER(ctypes.c_uint16)
-    L.if_fir_psd_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(PsdConfig), f32p, u64, i32]
-    L.if_fir_psd_init.restype = u8
-    L.if_fir_psd_frame_count.argtypes = [vp, u64]
-    L.if_fir_psd_frame_count.restype = u64
-    L.if_fir_psd_process.argtypes = [vp, vp, u64, u16p, f32p, ctypes.POINTER(u32)]
-    L.if_fir_psd_process.restype = u8
-    L.if_fir_psd_process_device.argtypes = [vp, vp, u64, vp, vp, ctypes.POINTER(u32)]
-    L.if_fir_psd_process_device.restype = u8
-    L.if_fir_pfb_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(PfbConfig), f32p, u32, u64, i32]
-    L.if_fir_pfb_init.restype = u8
-    L.if_fir_pfb_frame_count.argtypes = [vp, u64]
-    L.if_fir_pfb_frame_count.restype = u64
-    L.if_fir_pfb_process.argtypes = [vp, vp, f32p, u64, ctypes.POINTER(u64)]
-    L.if_fir_pfb_process.restype = u8
-    L.if_fir_pfb_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
-    L.if_fir_pfb_process_device.restype = u8
-    L.if_fir_synth_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(SynthConfig), f32p, u32, u64, i32]
-    L.if_fir_synth_init.restype = u8
-    L.if_fir_synth_sample_count.argtypes = [vp, u64]
-    L.if_fir_synth_sample_count.restype = u64
-    L.if_fir_synth_process.argtypes = [vp, vp, f32p, u64, ctypes.POINTER(u64)]
-    L.if_fir_synth_process.restype = u8
-    L.if_fir_synth_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
-    L.if_fir_synth_process_device.restype = u8
-    L.if_fir_fpow_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(FpowConfig), u64, i32]
-    L.if_fir_fpow_init.restype = u8
-    L.if_fir_fpow_frame_count.argtypes = [vp, u64]
-    L.if_fir_fpow_frame_count.restype = u64
-    L.if_fir_fpow_process.argtypes = [vp, vp, u64, u16p, f32p, ctypes.POINTER(u32)]
-    L.if_fir_fpow_process.restype = u8
-    L.if_fir_fpow_process_device.argtypes = [vp, vp, u64, vp, vp, ctypes.POINTER(u32)]
-    L.if_fir_fpow_process_device.restype = u8
-    if dev:
-        L.if_fir_debug_fpow_config.argtypes = [vp, u32, u64]
-        L.if_fir_debug_fpow_config.restype = u8
-    # the corner turn carries no state: the common calls but no reset
-    for name, args, res in (("destroy", [vp], None), ("synchronize", [vp], u8), ("set_input_format", [vp, u32], u8),
-                            ("set_output_format", [vp, u32], u8), ("set_stream", [vp, vp], u8), ("last_error", [vp], ctypes.c_char_p),
-                            ("init", [ctypes.POINTER(vp), ctypes.POINTER(TurnConfig), ctypes.POINTER(u32), u64, i32], u8),
-                            ("process", [vp, vp, vp, u64, u64], u8), ("process_device", [vp, vp, vp, u64, u64], u8)):
-        getattr(L, "if_fir_turn_" + name).argtypes = args
-        getattr(L, "if_fir_turn_" + name).restype = res
-    if dev:
-        L.if_fir_debug_turn_config.argtypes = [vp, u32]
-        L.if_fir_debug_turn_config.restype = u8
-    L.if_fir_sub_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(SubConfig), f32p, u64, i32]
-    L.if_fir_sub_init.restype = u8
-    L.if_fir_sub_set_nco.argtypes = [vp, f64p]
-    L.if_fir_sub_set_nco.restype = u8
-    L.if_fir_sub_get_nco.argtypes = [vp, f64p]
-    L.if_fir_sub_get_nco.restype = u8
-    L.if_fir_sub_frame_count.argtypes = [vp, u64]
-    L.if_fir_sub_frame_count.restype = u64
-    L.if_fir_sub_process.argtypes = [vp, vp, f32p, u64, ctypes.POINTER(u64)]
-    L.if_fir_sub_process.restype = u8
-    L.if_fir_sub_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
-    L.if_fir_sub_process_device.restype = u8
-    if dev:
-        L.if_fir_debug_sub_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
-        L.if_fir_debug_sub_config.restype = u8
-    L.if_fir_subup_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(SubUpConfig), f32p, u64, i32]
-    L.if_fir_subup_init.restype = u8
-    L.if_fir_subup_set_nco.argtypes = [vp, f64p]
-    L.if_fir_subup_set_nco.restype = u8
-    L.if_fir_subup_get_nco.argtypes = [vp, f64p]
-    L.if_fir_subup_get_nco.restype = u8
-    L.if_fir_subup_frame_count.argtypes = [vp, u64]
-    L.if_fir_subup_frame_count.restype = u64
-    L.if_fir_subup_process.argtypes = [vp, vp, f32p, u64, ctypes.POINTER(u64)]
-    L.if_fir_subup_process.restype = u8
-    L.if_fir_subup_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
-    L.if_fir_subup_process_device.restype = u8
-    L.if_fir_rpfb_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(RpfbConfig), f32p, u32, u64, i32]
-    L.if_fir_rpfb_init.restype = u8
-    L.if_fir_rpfb_frame_count.argtypes = [vp, u64]
-    L.if_fir_rpfb_frame_count.restype = u64
-    L.if_fir_rpfb_process.argtypes = [vp, vp, f32p, u64, ctypes.POINTER(u64)]
-    L.if_fir_rpfb_process.restype = u8
-    L.if_fir_rpfb_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
-    L.if_fir_rpfb_process_device.restype = u8
-    L.if_fir_rsynth_init.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(RsynthConfig), f32p, u32, u64, i32]
-    L.if_fir_rsynth_init.restype = u8
-    L.if_fir_rsynth_set_output_format.argtypes = [vp, u32]
-    L.if_fir_rsynth_set_output_format.restype = u8
-    L.if_fir_rsynth_sample_count.argtypes = [vp, u64]
-    L.if_fir_rsynth_sample_count.restype = u64
-    L.if_fir_rsynth_process.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
-    L.if_fir_rsynth_process.restype = u8
-    L.if_fir_rsynth_process_device.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
-    L.if_fir_rsynth_process_device.restype = u8
-    if dev:
-        L.if_fir_debug_rsynth_config.argtypes = [vp, u32, u64]
-        L.if_fir_debug_rsynth_config.restype = u8
-        L.if_fir_debug_rsynth_workspace.argtypes = [vp, u64, ctypes.POINTER(u64)]
-        L.if_fir_debug_rsynth_workspace.restype = u8
-        L.if_fir_debug_rpfb_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
-        L.if_fir_debug_rpfb_config.restype = u8
-        L.if_fir_debug_subup_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
-        L.if_fir_debug_subup_config.restype = u8
-        L.if_fir_debug_synth_config.argtypes = [vp, u32, u32, ctypes.POINTER(u32), u64]
-        L.if_fir_debug_synth_config.restype = u8
-        L.if_fir_debug_synth_workspace.argtypes = [vp, u64, ctypes.POINTER(u64)]
-        L.if_fir_debug_synth_workspace.restype = u8
-        L.if_fir_debug_pfb_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
-        L.if_fir_debug_pfb_config.restype = u8
-        L.if_fir_debug_combiner_config.argtypes = [vp, u32]
-        L.if_fir_debug_combiner_config.restype = u8
-        L.if_fir_debug_combiner_seek.argtypes = [vp, u64]
-        L.if_fir_debug_combiner_seek.restype = u8
-        L.if_fir_debug_combiner_tables.argtypes = [f32p, u32, u32, ctypes.c_double, ctypes.POINTER(u32), ctypes.POINTER(i32), f32p, u32]
-        L.if_fir_debug_combiner_tables.restype = u32
-        L.if_fir_debug_psd_plan.argtypes = [vp, u64, ctypes.POINTER(u64)]
-        L.if_fir_debug_psd_plan.restype = u8
-        L.if_fir_debug_psd_config.argtypes = [vp, u32, u64]
-        L.if_fir_debug_psd_config.restype = u8
-        L.if_fir_debug_resamp_config.argtypes = [vp, u32, ctypes.POINTER(u32)]
-        L.if_fir_debug_resamp_config.restype = u8
-        L.if_fir_debug_ddc_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
-        L.if_fir_debug_ddc_config.restype = u8
-        L.if_fir_debug_duc_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64]
-        L.if_fir_debug_duc_config.restype = u8
-        L.if_fir_debug_arb_config.argtypes = [vp, u32, ctypes.POINTER(u32), u64, u64]
-        L.if_fir_debug_arb_config.restype = u8
-        L.if_fir_debug_interp_config.argtypes = [vp, u32, u32]
-        L.if_fir_debug_interp_config.restype = u8
-        L.if_fir_debug_interp_seek.argtypes = [vp, u64]
-        L.if_fir_debug_interp_seek.restype = u8
-        L.if_fir_debug_interp_tables.argtypes = [f32p, u32, u32, f32p, u32]
-        L.if_fir_debug_interp_tables.restype = u32
-        L.if_fir_debug_interp_plan.argtypes = [u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]
-        L.if_fir_debug_interp_plan.restype = u8
-        L.if_fir_time_device.argtypes = [vp, vp, vp, u64, u32, u32, f32p]
-        L.if_fir_time_device.restype = u8
-        L.if_fir_debug_stamps.argtypes = [vp, ctypes.POINTER(u64), u32]
-        L.if_fir_debug_stamps.restype = u32
-        L.if_fir_debug_fft_tables.argtypes = [f32p, u32, u32, u32, u32, f32p, u32]
-        L.if_fir_debug_fft_tables.restype = u32
-        L.if_fir_debug_fft_schedule.argtypes = [u64, u32, u32, ctypes.POINTER(ctypes.c_int64)]
-        L.if_fir_debug_fft_schedule.restype = u8
-        L.if_fir_mc_debug_plan.argtypes = [u32, u32, u32, u64, u32, u32, u32, u64, u64, ctypes.POINTER(u64), u32]
-        L.if_fir_mc_debug_plan.restype = u32
-        L.if_fir_debug_queue_faults.argtypes = [vp, ctypes.POINTER(u32)]
-        L.if_fir_debug_queue_faults.restype = u8
+    for table in (ABI, DEV_ABI) if dev else (ABI,):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _libs[path] = L
     return L
 
 
 def _f32p(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+_DUMMY = np.zeros(2, dtype=np.float32)   # where the pointers of an empty call point: the C side refuses NULL even for no data
+
+
+def _host_ptr(a, as_type=ctypes.c_void_p):
+    """pointer (void *, or as_type) to the data of a host array that a streaming process() sends or fills; _DUMMY if it is empty"""
+    return (a if a.size else _DUMMY).ctypes.data_as(as_type)
 
 
 def _taps_arg(taps, complex_taps):
@@ -683,13 +471,31 @@ class IfFir:
 
 
 class _StreamCtx:
-    """What IfFirInterp, IfFirResamp, IfFirPsd, IfFirCombiner, IfFirDdc, IfFirDuc, IfFirArb, IfFirPfb, IfFirSynth, IfFirSub, IfFirSubUp, IfFirRpfb, IfFirRsynth, IfFirFpow and IfFirTurn share (csrc/if_fir_stream_ctx.h is the C side of it): the context's lifetime, the
-    calls the fifteen families have under one name, and the host array a process() sends.  A subclass sets _PREFIX and, in its
-    __init__, self._L, self._ctx and self._i16."""
-    _PREFIX = None   # the family's C name prefix: "if_fir_interp_" and so on
+    """What the streaming families share (csrc/if_fir_stream_ctx.h is the C side of it), under that header's rule: nothing here
+    branches on which family calls it; a difference comes in as an argument or a class attribute.  The base holds the frame of a
+    constructor (_open first, _init last), the context's lifetime, the calls every family has under one name, the host arrays a
+    process() sends, the counted process() and process_device() calls, the count query, NO_POSITION and the guard of the
+    development hooks.  What only some families have is in the mixins below.  A family sets _FAMILY and keeps what is its own:
+    its constructor's arguments and refusals, its process() -- what it allocates and returns -- and its debug calls."""
+    _FAMILY = None                 # "interp": the C names are if_fir_interp_<call> and if_fir_debug_interp_<call>
+    NO_POSITION = (1 << 64) - 1    # the position of a debug_config that leaves the stream where it is
 
-    def _c(self, name):
-        return getattr(self._L, self._PREFIX + name)
+    def _c(self, call):
+        return getattr(self._L, "if_fir_%s_%s" % (self._FAMILY, call))
+
+    def _open(self, dev):
+        """First in a constructor: the library, no context yet, float32 in and out."""
+        self._L = dev_lib() if dev else lib()
+        self._ctx = ctypes.c_void_p()
+        self._dev, self._grid_limit = bool(dev), 0
+        self._i16 = self._o16 = False
+        self._process_device_c = self._c("process_device")   # looked up once: process_device is the call made per chunk
+
+    def _init(self, call, *args):
+        """Last in a constructor: <prefix><call>(&context, *args); a refusal leaves no context and raises the library's message."""
+        if not self._c(call)(ctypes.byref(self._ctx), *args):
+            self._ctx = ctypes.c_void_p()
+            raise IfFirError(self._c("last_error")(None).decode())
 
     def _check(self, ok):
         if not ok:
@@ -725,6 +531,10 @@ class _StreamCtx:
     def synchronize(self):
         self._check(self._c("synchronize")(self._ctx))
 
+    def _count(self, call, n):
+        """<prefix>out_count(), frame_count() or sample_count(): what a call with n inputs emits at the current stream position"""
+        return int(self._c(call)(self._ctx, int(n)))
+
     def _host_input(self, iq):
         """(contiguous interleaved float32 -- or int16 after set_input_format(INPUT_I16) -- array, sample count) of a host array"""
         iq = np.asarray(iq)
@@ -736,62 +546,151 @@ class _StreamCtx:
             iq = np.ascontiguousarray(iq, dtype=np.float32).reshape(-1)
         return iq, iq.size // 2
 
+    def _frames_input(self, frames):
+        """(contiguous array, frame count) of a host (frames, bins) array: complex64 / interleaved float32, or int16 pairs after
+        set_input_format(INPUT_I16)"""
+        x, n = self._host_input(frames)
+        if n % self.bins:
+            raise IfFirError("if_fir_%s_process: %d elements are not whole frames of %d bins" % (self._FAMILY, n, self.bins))
+        return x, n // self.bins
+
+    def _process_host(self, src, out, count, out_type=_F32P):
+        """<prefix>process() in its counted form: `count` units of the host array src in, the host array out (passed as out_type,
+        the type the family declares) filled; returns the count the call reports"""
+        m = ctypes.c_uint64(0)
+        self._check(self._c("process")(self._ctx, _host_ptr(src), _host_ptr(out, out_type), count, ctypes.byref(m)))
+        return int(m.value)
+
     def _process(self, iq):
         """<prefix>process() of a family with one input and one output stream: host array in, interleaved float32 out"""
         iq, n = self._host_input(iq)
         out = np.empty(2 * self.out_count(n), dtype=np.float32)
-        m = ctypes.c_uint64(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._c("process")(self._ctx, ctypes.c_void_p(iq.ctypes.data if n else dummy.ctypes.data),
-                                       _f32p(out if out.size else dummy), n, ctypes.byref(m)))
-        assert m.value * 2 == out.size
+        m = self._process_host(iq, out, n)
+        assert m * 2 == out.size
         return out
 
-    def _process_device(self, dev_in, dev_out, samples):
-        """<prefix>process_device() of such a family: raw device pointers (ints), asynchronous; the output sample count"""
+    def _process_device(self, dev_in, dev_out, count):
+        """<prefix>process_device() in its counted form: raw device pointers (ints), asynchronous; the count the call reports"""
         m = ctypes.c_uint64(0)
-        self._check(self._c("process_device")(self._ctx, ctypes.c_void_p(dev_in), ctypes.c_void_p(dev_out), int(samples),
-                                              ctypes.byref(m)))
+        if not self._process_device_c(self._ctx, ctypes.c_void_p(dev_in), ctypes.c_void_p(dev_out), int(count), ctypes.byref(m)):
+            self._check(False)   # (asked only on failure: the per-chunk call costs a family no more Python than its own copy did)
+        return int(m.value)
+
+    def _debug(self, call):
+        """The development hook if_fir_debug_<family>_<call>; refused unless the context was made with dev=True."""
+        name = "if_fir_debug_%s_%s" % (self._FAMILY, call)
+        if not self._dev:
+            raise IfFirError("%s is in the development library only: construct with dev=True" % name)
+        return getattr(self._L, name)
+
+    def _position(self, position):
+        return self.NO_POSITION if position is None else int(position)
+
+    def _debug_config_tile(self, grid_limit, position):
+        """if_fir_debug_<family>_config(context, grid limit, &tile, position): returns the tile (what it counts is the family's)"""
+        tile = ctypes.c_uint32(0)
+        self._check(self._debug("config")(self._ctx, int(grid_limit), ctypes.byref(tile), self._position(position)))
+        self._grid_limit = int(grid_limit)
+        return int(tile.value)
+
+
+class _RealInput:
+    """Families that take REAL samples (IfFirDdc, IfFirRpfb)."""
+
+    def _host_input(self, r):
+        """(contiguous float32 -- or int16 after set_input_format(INPUT_I16) -- array of REAL samples, sample count)"""
+        r = np.ascontiguousarray(r, dtype=np.int16 if self._i16 else np.float32).reshape(-1)
+        return r, r.size
+
+
+class _ScalarNco:
+    """Families with one NCO (IfFirInterp, IfFirDdc, IfFirDuc); which way it mixes, and by which index, is the family's."""
+
+    def set_nco(self, freq):
+        """<prefix>set_nco(): the NCO frequency in cycles per sample; 0 = off."""
+        self._check(self._c("set_nco")(self._ctx, float(freq)))
+
+    def get_nco(self):
+        f = ctypes.c_double(0.0)
+        self._check(self._c("get_nco")(self._ctx, ctypes.byref(f)))
+        return float(f.value)
+
+
+class _BinNco:
+    """Families with one NCO per bin of a frame (IfFirSub, IfFirSubUp)."""
+
+    def set_nco(self, freqs):
+        """<prefix>set_nco(): `bins` frequencies in cycles per frame of the family's NCO rate, |f| <= 0.5; None sets every word
+        to 0."""
+        if freqs is None:
+            self._check(self._c("set_nco")(self._ctx, None))
+            return
+        f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        if f.size != self.bins:
+            raise IfFirError("if_fir_%s_set_nco: %d frequencies for %d bins" % (self._FAMILY, f.size, self.bins))
+        self._check(self._c("set_nco")(self._ctx, f.ctypes.data_as(_F64P)))
+
+    def get_nco(self):
+        """<prefix>get_nco(): the quantised frequencies in force, one per bin."""
+        f = np.zeros(self.bins, dtype=np.float64)
+        self._check(self._c("get_nco")(self._ctx, f.ctypes.data_as(_F64P)))
+        return f
+
+
+class _OutputFormat:
+    """Families that can emit int16 (IfFirDuc, IfFirRsynth, IfFirTurn)."""
+
+    def set_output_format(self, fmt):
+        """<prefix>set_output_format(): OUTPUT_F32 or OUTPUT_I16 (the float32 result times 2^15, to nearest even, saturated)."""
+        self._check(self._c("set_output_format")(self._ctx, int(fmt)))
+        self._o16 = (int(fmt) == OUTPUT_I16)
+
+
+class _CodeFrames:
+    """Families that emit frames of uint16 spectrum codes and, optionally, float32 powers (IfFirPsd, IfFirFpow)."""
+
+    def _process_codes(self, src, count, frames, width, want_power):
+        """<prefix>process(): `count` units of the host array src in; returns ((frames, width) uint16 codes, float32 powers of
+        that shape or None)"""
+        codes = np.empty((frames, width), dtype=np.uint16)
+        power = np.empty((frames, width), dtype=np.float32) if want_power else None
+        m = ctypes.c_uint32(0)
+        self._check(self._c("process")(self._ctx, _host_ptr(src), count, codes.ctypes.data_as(_U16P) if frames else None,
+                                       _f32p(power) if want_power and frames else None, ctypes.byref(m)))
+        assert m.value == frames
+        return codes, power
+
+    def _process_codes_device(self, dev_in, count, dev_bins, dev_power):
+        """<prefix>process_device(): raw device pointers (ints; dev_power may be 0), asynchronous; the frames emitted"""
+        m = ctypes.c_uint32(0)
+        self._check(self._process_device_c(self._ctx, ctypes.c_void_p(dev_in or None), int(count), ctypes.c_void_p(dev_bins or None),
+                                           ctypes.c_void_p(dev_power or None), ctypes.byref(m)))
         return int(m.value)
 
 
-class IfFirInterp(_StreamCtx):
+class IfFirInterp(_ScalarNco, _StreamCtx):
     """One if_fir_interp_t: upsample by `interpolation`, filter, optionally mix up (docs/SPEC.md §6).  Methods mirror the C
-    entry points; N input samples give N * interpolation outputs."""
-    _PREFIX = "if_fir_interp_"
+    entry points; N input samples give N * interpolation outputs.  set_nco(f) mixes the OUTPUT up by exp(+j 2 pi f n), n =
+    absolute output index."""
+    _FAMILY = "interp"
 
     def __init__(self, taps, interpolation, max_samples=1 << 20, device=0, backend=None, complex_taps=False, dev=False):
-        self._L = dev_lib() if dev else lib()
+        self._open(dev)
         taps, count, complex_taps = _taps_arg(taps, complex_taps)
-        self._ctx = ctypes.c_void_p()
         self.taps = taps
         self.interpolation = int(interpolation)
-        self._i16 = False
-        init = self._L.if_fir_interp_init_complex if complex_taps else self._L.if_fir_interp_init
-        if not init(ctypes.byref(self._ctx), _f32p(taps), count, self.interpolation,
-                    int(max_samples), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
+        self._init("init_complex" if complex_taps else "init", _f32p(taps), count, self.interpolation, int(max_samples), int(device))
         if backend is not None:
             self.set_backend(backend)
 
     def set_backend(self, backend):
-        self._check(self._L.if_fir_interp_set_backend(self._ctx, int(backend)))
+        self._check(self._c("set_backend")(self._ctx, int(backend)))
 
     def get_backend(self):
-        return int(self._L.if_fir_interp_get_backend(self._ctx))
-
-    def set_nco(self, freq):
-        """if_fir_interp_set_nco(): mix the OUTPUT up by exp(+j 2 pi f n), n = absolute output index; 0 = off."""
-        self._check(self._L.if_fir_interp_set_nco(self._ctx, float(freq)))
-
-    def get_nco(self):
-        f = ctypes.c_double(0.0)
-        self._check(self._L.if_fir_interp_get_nco(self._ctx, ctypes.byref(f)))
-        return float(f.value)
+        return int(self._c("get_backend")(self._ctx))
 
     def out_count(self, samples):
-        return int(self._L.if_fir_interp_out_count(self._ctx, int(samples)))
+        return self._count("out_count", samples)
 
     def process(self, iq):
         """if_fir_interp_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in,
@@ -835,45 +734,40 @@ class IfFirCombiner(_StreamCtx):
     """One if_fir_combiner_t: C baseband streams, each interpolated by `interpolation` with one prototype filter and mixed up to
     its own centre, summed into one stream in one pass (docs/SPEC.md §9).  Methods mirror the C entry points; N input samples per
     channel give N * interpolation outputs."""
-    _PREFIX = "if_fir_combiner_"
+    _FAMILY = "combiner"
 
     def __init__(self, taps, interpolation, centres, max_samples=1 << 20, device=0, backend=None, complex_taps=False, dev=False):
-        self._L = dev_lib() if dev else lib()
+        self._open(dev)
         taps, count, complex_taps = _taps_arg(taps, complex_taps)
         centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1)
-        self._ctx = ctypes.c_void_p()
         self.taps = taps
         self.interpolation = int(interpolation)
         self.channels = int(centres.size)
-        self._i16 = False
-        init = self._L.if_fir_combiner_init_complex if complex_taps else self._L.if_fir_combiner_init
-        if not init(ctypes.byref(self._ctx), _f32p(taps), count, self.interpolation,
-                    self.channels, centres.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(max_samples), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
+        self._init("init_complex" if complex_taps else "init", _f32p(taps), count, self.interpolation, self.channels,
+                   centres.ctypes.data_as(_F64P), int(max_samples), int(device))
         if backend is not None:
             self.set_backend(backend)
 
     def set_backend(self, backend):
-        self._check(self._L.if_fir_combiner_set_backend(self._ctx, int(backend)))
+        self._check(self._c("set_backend")(self._ctx, int(backend)))
 
     def get_backend(self):
-        return int(self._L.if_fir_combiner_get_backend(self._ctx))
+        return int(self._c("get_backend")(self._ctx))
 
     def set_centres(self, centres):
         """if_fir_combiner_set_centres(): all centres at once, from the next call, as if set since the last reset."""
         centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1)
         if centres.size != self.channels:
             raise IfFirError("if_fir_combiner_set_centres takes %d centres (got %d)" % (self.channels, centres.size))
-        self._check(self._L.if_fir_combiner_set_centres(self._ctx, centres.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        self._check(self._c("set_centres")(self._ctx, centres.ctypes.data_as(_F64P)))
 
     def get_centres(self):
         f = np.zeros(self.channels, dtype=np.float64)
-        self._check(self._L.if_fir_combiner_get_centres(self._ctx, f.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        self._check(self._c("get_centres")(self._ctx, f.ctypes.data_as(_F64P)))
         return f
 
     def out_count(self, samples):
-        return int(self._L.if_fir_combiner_out_count(self._ctx, int(samples)))
+        return self._count("out_count", samples)
 
     def process(self, iqs):
         """if_fir_combiner_process(): one host array per channel (interleaved float32 / complex64, or int16 pairs after
@@ -886,9 +780,8 @@ class IfFirCombiner(_StreamCtx):
             raise IfFirError("if_fir_combiner_process: every channel brings the same number of samples")
         out = np.empty(2 * self.out_count(n), dtype=np.float32)
         m = ctypes.c_uint64(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        ptrs = (ctypes.c_void_p * self.channels)(*[a[0].ctypes.data if n else dummy.ctypes.data for a in arrs])
-        self._check(self._L.if_fir_combiner_process(self._ctx, ptrs, _f32p(out if out.size else dummy), n, ctypes.byref(m)))
+        ptrs = (ctypes.c_void_p * self.channels)(*[_host_ptr(a[0]) for a in arrs])
+        self._check(self._c("process")(self._ctx, ptrs, _host_ptr(out, _F32P), n, ctypes.byref(m)))
         assert m.value * 2 == out.size
         return out
 
@@ -899,7 +792,7 @@ class IfFirCombiner(_StreamCtx):
             raise IfFirError("if_fir_combiner_process_device takes %d channels (got %d)" % (self.channels, len(dev_ins)))
         m = ctypes.c_uint64(0)
         ptrs = (ctypes.c_void_p * self.channels)(*[int(p) for p in dev_ins])
-        self._check(self._L.if_fir_combiner_process_device(self._ctx, ptrs, ctypes.c_void_p(dev_out), int(samples), ctypes.byref(m)))
+        self._check(self._process_device_c(self._ctx, ptrs, ctypes.c_void_p(dev_out), int(samples), ctypes.byref(m)))
         return int(m.value)
 
     def debug_config(self, grid_limit=0):
@@ -927,25 +820,19 @@ def debug_combiner_tables(taps, centre, complex_taps=False):
 class IfFirResamp(_StreamCtx):
     """One if_fir_resamp_t: change the rate by interpolation / decimation in one polyphase pass (docs/SPEC.md §7).  Methods
     mirror the C entry points; how many outputs a call emits depends on the stream position (out_count)."""
-    _PREFIX = "if_fir_resamp_"
+    _FAMILY = "resamp"
 
     def __init__(self, taps, interpolation, decimation, max_samples=1 << 20, device=0, complex_taps=False, dev=False):
-        self._L = dev_lib() if dev else lib()
+        self._open(dev)
         taps, count, complex_taps = _taps_arg(taps, complex_taps)
-        self._ctx = ctypes.c_void_p()
         self.taps = taps
         self.interpolation, self.decimation = int(interpolation), int(decimation)
-        self._i16 = False
-        self._dev, self._grid_limit = bool(dev), 0
-        init = self._L.if_fir_resamp_init_complex if complex_taps else self._L.if_fir_resamp_init
-        if not init(ctypes.byref(self._ctx), _f32p(taps), count, self.interpolation,
-                    self.decimation, int(max_samples), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
+        self._init("init_complex" if complex_taps else "init", _f32p(taps), count, self.interpolation, self.decimation,
+                   int(max_samples), int(device))
 
     def out_count(self, samples):
         """if_fir_resamp_out_count(): outputs of a call with `samples` inputs at the current stream position."""
-        return int(self._L.if_fir_resamp_out_count(self._ctx, int(samples)))
+        return self._count("out_count", samples)
 
     def process(self, iq):
         """if_fir_resamp_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in,
@@ -959,10 +846,8 @@ class IfFirResamp(_StreamCtx):
     def debug_config(self, grid_limit=0):
         """if_fir_debug_resamp_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
         launcher's choice).  Returns the outputs of one tile of this context."""
-        if not self._dev:
-            raise IfFirError("if_fir_debug_resamp_config is in the development library only: construct with dev=True")
         tile = ctypes.c_uint32(0)
-        self._check(self._L.if_fir_debug_resamp_config(self._ctx, int(grid_limit), ctypes.byref(tile)))
+        self._check(self._debug("config")(self._ctx, int(grid_limit), ctypes.byref(tile)))
         self._grid_limit = int(grid_limit)
         return int(tile.value)
 
@@ -981,22 +866,16 @@ class IfFirArb(_StreamCtx):
     """One if_fir_arb_t: change the rate by any ratio 1/64 .. 4 with a step that can be retuned between calls (docs/SPEC.md
     §12).  `taps` is the real prototype designed at 2^phase_bits times the input rate; `step` is input samples per output
     sample times 2^32.  Methods mirror the C entry points; how many outputs a call emits depends on the position (out_count)."""
-    _PREFIX = "if_fir_arb_"
+    _FAMILY = "arb"
 
     def __init__(self, taps, phase_bits, step, max_samples=1 << 20, device=0, dev=False):
-        self._L = dev_lib() if dev else lib()
+        self._open(dev)
         taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
-        self._ctx = ctypes.c_void_p()
         self.taps = taps
         self.phase_bits, self._step = int(phase_bits), int(step)
-        self._i16 = False
-        self._dev, self._grid_limit = bool(dev), 0
         if not (0 <= self.phase_bits < 1 << 32 and 0 <= self._step < 1 << 64):
             raise IfFirError("if_fir_arb_init: phase bits and step must be unsigned (got %d, %d)" % (self.phase_bits, self._step))
-        if not self._L.if_fir_arb_init(ctypes.byref(self._ctx), _f32p(taps), taps.size, self.phase_bits, self._step,
-                                       int(max_samples), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
+        self._init("init", _f32p(taps), taps.size, self.phase_bits, self._step, int(max_samples), int(device))
 
     @property
     def step(self):
@@ -1007,12 +886,12 @@ class IfFirArb(_StreamCtx):
         """if_fir_arb_set_step(): retune between calls; the position, the time of the next output and the history stay."""
         if not 0 <= int(step) < 1 << 64:
             raise IfFirError("if_fir_arb_set_step: step must be 2^26..2^34 (got %d)" % int(step))
-        self._check(self._L.if_fir_arb_set_step(self._ctx, int(step)))
+        self._check(self._c("set_step")(self._ctx, int(step)))
         self._step = int(step)
 
     def out_count(self, samples):
         """if_fir_arb_out_count(): outputs of a call with `samples` inputs at the current position and step."""
-        return int(self._L.if_fir_arb_out_count(self._ctx, int(samples)))
+        return self._count("out_count", samples)
 
     def process(self, iq):
         """if_fir_arb_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in,
@@ -1027,11 +906,8 @@ class IfFirArb(_StreamCtx):
         """if_fir_debug_arb_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
         launcher's choice); with `position`, on a freshly reset context, the next input has that absolute index and the next
         output comes time_offset / 2^32 samples after it.  Returns the outputs of one tile of this context."""
-        if not self._dev:
-            raise IfFirError("if_fir_debug_arb_config is in the development library only: construct with dev=True")
         tile = ctypes.c_uint32(0)
-        pos = (1 << 64) - 1 if position is None else int(position)
-        self._check(self._L.if_fir_debug_arb_config(self._ctx, int(grid_limit), ctypes.byref(tile), pos, int(time_offset)))
+        self._check(self._debug("config")(self._ctx, int(grid_limit), ctypes.byref(tile), self._position(position), int(time_offset)))
         self._grid_limit = int(grid_limit)
         return int(tile.value)
 
@@ -1040,43 +916,22 @@ class IfFirArb(_StreamCtx):
         return self.debug_config(self._grid_limit)
 
 
-class IfFirDdc(_StreamCtx):
+class IfFirDdc(_RealInput, _ScalarNco, _StreamCtx):
     """One if_fir_ddc_t: REAL IF samples to decimated complex baseband in one pass -- NCO down-mix, filter, keep every
     decimation-th (docs/SPEC.md §10).  Methods mirror the C entry points; how many outputs a call emits depends on the stream
-    position (out_count)."""
-    _PREFIX = "if_fir_ddc_"
-    NO_POSITION = (1 << 64) - 1
+    position (out_count).  set_nco(f) mixes the input down by exp(-j 2 pi f a), a = absolute sample index."""
+    _FAMILY = "ddc"
 
     def __init__(self, taps, decimation, max_samples=1 << 20, device=0, complex_taps=False, dev=False):
-        self._L = dev_lib() if dev else lib()
+        self._open(dev)
         taps, count, complex_taps = _taps_arg(taps, complex_taps)
-        self._ctx = ctypes.c_void_p()
         self.taps = taps
         self.decimation = int(decimation)
-        self._i16 = False
-        self._dev, self._grid_limit = bool(dev), 0
-        init = self._L.if_fir_ddc_init_complex if complex_taps else self._L.if_fir_ddc_init
-        if not init(ctypes.byref(self._ctx), _f32p(taps), count, self.decimation, int(max_samples), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
-
-    def set_nco(self, freq):
-        """if_fir_ddc_set_nco(): mix the input down by exp(-j 2 pi f a), a = absolute sample index; 0 = off."""
-        self._check(self._L.if_fir_ddc_set_nco(self._ctx, float(freq)))
-
-    def get_nco(self):
-        f = ctypes.c_double(0.0)
-        self._check(self._L.if_fir_ddc_get_nco(self._ctx, ctypes.byref(f)))
-        return float(f.value)
+        self._init("init_complex" if complex_taps else "init", _f32p(taps), count, self.decimation, int(max_samples), int(device))
 
     def out_count(self, samples):
         """if_fir_ddc_out_count(): outputs of a call with `samples` inputs at the current stream position."""
-        return int(self._L.if_fir_ddc_out_count(self._ctx, int(samples)))
-
-    def _host_input(self, r):
-        """(contiguous float32 -- or int16 after set_input_format(INPUT_I16) -- array of REAL samples, sample count)"""
-        r = np.ascontiguousarray(r, dtype=np.int16 if self._i16 else np.float32).reshape(-1)
-        return r, r.size
+        return self._count("out_count", samples)
 
     def process(self, r):
         """if_fir_ddc_process(): host float32 (or int16 after set_input_format(INPUT_I16)) real samples in, interleaved
@@ -1091,67 +946,38 @@ class IfFirDdc(_StreamCtx):
         """if_fir_debug_ddc_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
         launcher's choice); position (optional) = the absolute index of the next call's first sample, with the history zeroed.
         Returns the outputs of one tile of this context."""
-        if not self._dev:
-            raise IfFirError("if_fir_debug_ddc_config is in the development library only: construct with dev=True")
-        tile = ctypes.c_uint32(0)
-        self._check(self._L.if_fir_debug_ddc_config(self._ctx, int(grid_limit), ctypes.byref(tile),
-                                                    self.NO_POSITION if position is None else int(position)))
-        self._grid_limit = int(grid_limit)
-        return int(tile.value)
+        return self._debug_config_tile(grid_limit, position)
 
     def tile_outputs(self):
         """outputs one workgroup computes per tile (development library); the grid limit stays as it is"""
         return self.debug_config(self._grid_limit)
 
 
-class IfFirDuc(_StreamCtx):
+class IfFirDuc(_ScalarNco, _OutputFormat, _StreamCtx):
     """One if_fir_duc_t: complex baseband to a REAL IF stream at `interpolation` times the rate in one pass -- upsample, filter,
     NCO up-mix, real part, optionally int16 (docs/SPEC.md §11).  Methods mirror the C entry points; N input samples give
-    N * interpolation real outputs, float32 or (after set_output_format(OUTPUT_I16)) int16."""
-    _PREFIX = "if_fir_duc_"
-    NO_POSITION = (1 << 64) - 1
+    N * interpolation real outputs, float32 or (after set_output_format(OUTPUT_I16)) int16.  set_nco(f) mixes the output up by
+    exp(+j 2 pi f m), m = absolute output index, before the real part."""
+    _FAMILY = "duc"
 
     def __init__(self, taps, interpolation, max_samples=1 << 20, device=0, complex_taps=False, dev=False):
-        self._L = dev_lib() if dev else lib()
+        self._open(dev)
         taps, count, complex_taps = _taps_arg(taps, complex_taps)
-        self._ctx = ctypes.c_void_p()
         self.taps = taps
         self.interpolation = int(interpolation)
-        self._i16 = self._o16 = False
-        self._dev, self._grid_limit = bool(dev), 0
-        init = self._L.if_fir_duc_init_complex if complex_taps else self._L.if_fir_duc_init
-        if not init(ctypes.byref(self._ctx), _f32p(taps), count, self.interpolation, int(max_samples), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
-
-    def set_output_format(self, fmt):
-        """if_fir_duc_set_output_format(): OUTPUT_F32 or OUTPUT_I16 (the float32 result times 2^15, to nearest even, saturated)."""
-        self._check(self._L.if_fir_duc_set_output_format(self._ctx, int(fmt)))
-        self._o16 = (int(fmt) == OUTPUT_I16)
-
-    def set_nco(self, freq):
-        """if_fir_duc_set_nco(): mix the output up by exp(+j 2 pi f m), m = absolute output index, before the real part; 0 = off."""
-        self._check(self._L.if_fir_duc_set_nco(self._ctx, float(freq)))
-
-    def get_nco(self):
-        f = ctypes.c_double(0.0)
-        self._check(self._L.if_fir_duc_get_nco(self._ctx, ctypes.byref(f)))
-        return float(f.value)
+        self._init("init_complex" if complex_taps else "init", _f32p(taps), count, self.interpolation, int(max_samples), int(device))
 
     def out_count(self, samples):
         """if_fir_duc_out_count(): samples * interpolation."""
-        return int(self._L.if_fir_duc_out_count(self._ctx, int(samples)))
+        return self._count("out_count", samples)
 
     def process(self, iq):
         """if_fir_duc_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in, real
         float32 (or int16 after set_output_format(OUTPUT_I16)) out."""
         iq, n = self._host_input(iq)
         out = np.empty(self.out_count(n), dtype=np.int16 if self._o16 else np.float32)
-        m = ctypes.c_uint64(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._L.if_fir_duc_process(self._ctx, ctypes.c_void_p(iq.ctypes.data if n else dummy.ctypes.data),
-                                               ctypes.c_void_p(out.ctypes.data if out.size else dummy.ctypes.data), n, ctypes.byref(m)))
-        assert m.value == out.size
+        m = self._process_host(iq, out, n, ctypes.c_void_p)
+        assert m == out.size
         return out
 
     def process_device(self, dev_in, dev_out, samples):
@@ -1162,31 +988,22 @@ class IfFirDuc(_StreamCtx):
         """if_fir_debug_duc_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
         launcher's choice); position (optional) = the count of input samples before the next call, with the history zeroed.
         Returns the INPUT samples of one tile of this context."""
-        if not self._dev:
-            raise IfFirError("if_fir_debug_duc_config is in the development library only: construct with dev=True")
-        tile = ctypes.c_uint32(0)
-        self._check(self._L.if_fir_debug_duc_config(self._ctx, int(grid_limit), ctypes.byref(tile),
-                                                    self.NO_POSITION if position is None else int(position)))
-        self._grid_limit = int(grid_limit)
-        return int(tile.value)
+        return self._debug_config_tile(grid_limit, position)
 
     def tile_inputs(self):
         """input samples one workgroup takes per tile (development library); the grid limit stays as it is"""
         return self.debug_config(self._grid_limit)
 
 
-class IfFirPsd(_StreamCtx):
+class IfFirPsd(_CodeFrames, _StreamCtx):
     """One if_fir_psd_t: averaged periodogram of an IQ stream as frames of uint16 spectrum codes, the layout wb_detect reads
     (docs/SPEC.md §8).  Methods mirror the C entry points; how many frames a call emits depends on the stream position
     (frame_count)."""
-    _PREFIX = "if_fir_psd_"
-    NO_POSITION = (1 << 64) - 1
+    _FAMILY = "psd"
 
     def __init__(self, size, hop, segments, first_bin, bins, ref_power=1.0, window=None, input_format=INPUT_F32,
                  max_samples=1 << 20, device=0, dev=False):
-        self._L = dev_lib() if dev else lib()
-        self._ctx = ctypes.c_void_p()
-        self._dev = bool(dev)
+        self._open(dev)
         self.size, self.hop, self.segments, self.first_bin, self.bins = int(size), int(hop), int(segments), int(first_bin), int(bins)
         cfg = PsdConfig(self.size, self.hop, self.segments, self.first_bin, self.bins, float(ref_power), int(input_format))
         self._i16 = (int(input_format) == INPUT_I16)
@@ -1196,593 +1013,369 @@ class IfFirPsd(_StreamCtx):
             if window.size != self.size:
                 raise IfFirError("IfFirPsd: the window must have size = %d values (got %d)" % (self.size, window.size))
             wp = _f32p(window)
-        if not self._L.if_fir_psd_init(ctypes.byref(self._ctx), ctypes.byref(cfg), wp, int(max_samples), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
+        self._init("init", ctypes.byref(cfg), wp, int(max_samples), int(device))
 
     def frame_count(self, samples):
         """if_fir_psd_frame_count(): frames of a call with `samples` samples at the current stream position."""
-        return int(self._L.if_fir_psd_frame_count(self._ctx, int(samples)))
+        return self._count("frame_count", samples)
 
     def process(self, iq, want_power=True):
         """if_fir_psd_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in;
         returns ((frames, bins) uint16 codes, (frames, bins) float32 power or None)."""
         iq, n = self._host_input(iq)
-        frames = self.frame_count(n)
-        codes = np.empty((frames, self.bins), dtype=np.uint16)
-        power = np.empty((frames, self.bins), dtype=np.float32) if want_power else None
-        m = ctypes.c_uint32(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._L.if_fir_psd_process(
-            self._ctx, ctypes.c_void_p(iq.ctypes.data if n else dummy.ctypes.data), n,
-            codes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)) if frames else None,
-            _f32p(power) if want_power and frames else None, ctypes.byref(m)))
-        assert m.value == frames
-        return codes, power
+        return self._process_codes(iq, n, self.frame_count(n), self.bins, want_power)
 
     def process_device(self, dev_in, samples, dev_bins, dev_power=0):
         """if_fir_psd_process_device(): raw device pointers (ints; dev_power may be 0), asynchronous.  Returns the frames emitted."""
-        m = ctypes.c_uint32(0)
-        self._check(self._L.if_fir_psd_process_device(self._ctx, ctypes.c_void_p(dev_in or None), int(samples),
-                                                      ctypes.c_void_p(dev_bins or None), ctypes.c_void_p(dev_power or None),
-                                                      ctypes.byref(m)))
-        return int(m.value)
+        return self._process_codes_device(dev_in, samples, dev_bins, dev_power)
 
     def debug_plan(self, samples):
         """if_fir_debug_psd_plan() (development library: construct with dev=True): (segments, chunks, frames, carried samples)
         of the next call of `samples` samples."""
-        if not self._dev:
-            raise IfFirError("if_fir_debug_psd_plan is in the development library only: construct with dev=True")
         out = (ctypes.c_uint64 * 4)()
-        self._check(self._L.if_fir_debug_psd_plan(self._ctx, int(samples), out))
+        self._check(self._debug("plan")(self._ctx, int(samples), out))
         return tuple(int(v) for v in out)
 
     def debug_config(self, grid_limit=0, position=None):
         """if_fir_debug_psd_config() (development library: construct with dev=True): at most grid_limit workgroups of the chunk
         kernel (0 = the launcher's choice); position (optional) = the stream position of the next call's first sample, the first
         sample of a chunk, with nothing carried and the open frame's accumulator at +0."""
-        if not self._dev:
-            raise IfFirError("if_fir_debug_psd_config is in the development library only: construct with dev=True")
-        self._check(self._L.if_fir_debug_psd_config(self._ctx, int(grid_limit),
-                                                    self.NO_POSITION if position is None else int(position)))
+        self._check(self._debug("config")(self._ctx, int(grid_limit), self._position(position)))
 
 
 class IfFirPfb(_StreamCtx):
     """One if_fir_pfb_t: all `channels` channels of a uniform grid out of one IQ stream in one pass, a frame of `bins` complex64
     values every `hop` input samples (docs/SPEC.md §13).  Methods mirror the C entry points; how many frames a call emits
     depends on the stream position (frame_count)."""
-    _PREFIX = "if_fir_pfb_"
-    NO_POSITION = (1 << 64) - 1
+    _FAMILY = "pfb"
 
     def __init__(self, taps, channels, hop=None, first_bin=0, bins=None, max_samples=1 << 20, device=0, dev=False):
-        self._L = dev_lib() if dev else lib()
-        self._ctx = ctypes.c_void_p()
-        self._dev, self._grid_limit = bool(dev), 0
+        self._open(dev)
         taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
         self.taps = taps
         self.channels = int(channels)
         self.hop = self.channels if hop is None else int(hop)
         self.first_bin = int(first_bin)
         self.bins = self.channels if bins is None else int(bins)
-        self._i16 = False
         if not all(0 <= v < 1 << 32 for v in (self.channels, self.hop, self.bins)) or not -(1 << 31) <= self.first_bin < 1 << 31:
             raise IfFirError("if_fir_pfb_init: channels, hop and bins must be unsigned, first_bin a 32-bit integer")
         cfg = PfbConfig(self.channels, self.hop, self.first_bin, self.bins)
-        if not self._L.if_fir_pfb_init(ctypes.byref(self._ctx), ctypes.byref(cfg), _f32p(taps) if taps.size else None, taps.size,
-                                       int(max_samples), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
+        self._init("init", ctypes.byref(cfg), _f32p(taps) if taps.size else None, taps.size, int(max_samples), int(device))
 
     def frame_count(self, samples):
         """if_fir_pfb_frame_count(): frames of a call with `samples` samples at the current stream position."""
-        return int(self._L.if_fir_pfb_frame_count(self._ctx, int(samples)))
+        return self._count("frame_count", samples)
 
     def process(self, iq):
         """if_fir_pfb_process(): host interleaved float32 / complex64 (or int16 pairs after set_input_format(INPUT_I16)) in;
         returns the (frames, bins) complex64 array."""
         iq, n = self._host_input(iq)
-        frames = self.frame_count(n)
-        out = np.empty((frames, self.bins), dtype=np.complex64)
-        m = ctypes.c_uint64(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._L.if_fir_pfb_process(self._ctx, ctypes.c_void_p(iq.ctypes.data if n else dummy.ctypes.data),
-                                               _f32p(out.view(np.float32) if out.size else dummy), n, ctypes.byref(m)))
-        assert m.value == frames
+        out = np.empty((self.frame_count(n), self.bins), dtype=np.complex64)
+        m = self._process_host(iq, out, n)
+        assert m == out.shape[0]
         return out
 
     def process_device(self, dev_in, dev_out, samples):
         """if_fir_pfb_process_device(): raw device pointers (ints), asynchronous.  Returns the frames emitted."""
-        m = ctypes.c_uint64(0)
-        self._check(self._L.if_fir_pfb_process_device(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
-                                                      int(samples), ctypes.byref(m)))
-        return int(m.value)
+        return self._process_device(dev_in, dev_out, samples)
 
     def debug_config(self, grid_limit=0, position=None):
         """if_fir_debug_pfb_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
         launcher's choice); position (optional) = the absolute index of the next call's first sample, with the history zeroed.
         Returns the consecutive frames one workgroup owns."""
-        if not self._dev:
-            raise IfFirError("if_fir_debug_pfb_config is in the development library only: construct with dev=True")
-        group = ctypes.c_uint32(0)
-        self._check(self._L.if_fir_debug_pfb_config(self._ctx, int(grid_limit), ctypes.byref(group),
-                                                    self.NO_POSITION if position is None else int(position)))
-        self._grid_limit = int(grid_limit)
-        return int(group.value)
+        return self._debug_config_tile(grid_limit, position)
 
 
-class IfFirRpfb(_StreamCtx):
+class IfFirRpfb(_RealInput, _StreamCtx):
     """One if_fir_rpfb_t: the `channels` / 2 + 1 distinct channels of a uniform grid out of one REAL sample stream in one pass, a
     frame of `bins` complex64 values every `hop` input samples (docs/SPEC.md §17).  Methods mirror the C entry points; how many
     frames a call emits depends on the stream position (frame_count)."""
-    _PREFIX = "if_fir_rpfb_"
-    NO_POSITION = (1 << 64) - 1
+    _FAMILY = "rpfb"
 
     def __init__(self, taps, channels, hop=None, first_bin=0, bins=None, max_samples=1 << 20, device=0, dev=False):
-        self._L = dev_lib() if dev else lib()
-        self._ctx = ctypes.c_void_p()
-        self._dev, self._grid_limit = bool(dev), 0
+        self._open(dev)
         taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
         self.taps = taps
         self.channels = int(channels)
         self.hop = self.channels if hop is None else int(hop)
         self.first_bin = int(first_bin)
         self.bins = self.channels // 2 + 1 - self.first_bin if bins is None else int(bins)
-        self._i16 = False
         if not all(0 <= v < 1 << 32 for v in (self.channels, self.hop, self.first_bin, self.bins)):
             raise IfFirError("if_fir_rpfb_init: channels, hop, first_bin and bins must be unsigned 32-bit integers")
         cfg = RpfbConfig(self.channels, self.hop, self.first_bin, self.bins)
-        if not self._L.if_fir_rpfb_init(ctypes.byref(self._ctx), ctypes.byref(cfg), _f32p(taps) if taps.size else None, taps.size,
-                                        int(max_samples), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
+        self._init("init", ctypes.byref(cfg), _f32p(taps) if taps.size else None, taps.size, int(max_samples), int(device))
 
     def frame_count(self, samples):
         """if_fir_rpfb_frame_count(): frames of a call with `samples` samples at the current stream position."""
-        return int(self._L.if_fir_rpfb_frame_count(self._ctx, int(samples)))
-
-    def _host_input(self, r):
-        """(contiguous float32 -- or int16 after set_input_format(INPUT_I16) -- array of REAL samples, sample count)"""
-        r = np.ascontiguousarray(r, dtype=np.int16 if self._i16 else np.float32).reshape(-1)
-        return r, r.size
+        return self._count("frame_count", samples)
 
     def process(self, r):
         """if_fir_rpfb_process(): host float32 (or int16 after set_input_format(INPUT_I16)) real samples in; returns the
         (frames, bins) complex64 array."""
         r, n = self._host_input(r)
-        frames = self.frame_count(n)
-        out = np.empty((frames, self.bins), dtype=np.complex64)
-        m = ctypes.c_uint64(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._L.if_fir_rpfb_process(self._ctx, ctypes.c_void_p(r.ctypes.data if n else dummy.ctypes.data),
-                                                _f32p(out.view(np.float32) if out.size else dummy), n, ctypes.byref(m)))
-        assert m.value == frames
+        out = np.empty((self.frame_count(n), self.bins), dtype=np.complex64)
+        m = self._process_host(r, out, n)
+        assert m == out.shape[0]
         return out
 
     def process_device(self, dev_in, dev_out, samples):
         """if_fir_rpfb_process_device(): raw device pointers (ints), asynchronous.  Returns the frames emitted."""
-        m = ctypes.c_uint64(0)
-        self._check(self._L.if_fir_rpfb_process_device(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
-                                                       int(samples), ctypes.byref(m)))
-        return int(m.value)
+        return self._process_device(dev_in, dev_out, samples)
 
     def debug_config(self, grid_limit=0, position=None):
         """if_fir_debug_rpfb_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
         launcher's choice); position (optional) = the absolute index of the next call's first sample, with the history zeroed.
         Returns the consecutive frames one workgroup owns."""
-        if not self._dev:
-            raise IfFirError("if_fir_debug_rpfb_config is in the development library only: construct with dev=True")
-        group = ctypes.c_uint32(0)
-        self._check(self._L.if_fir_debug_rpfb_config(self._ctx, int(grid_limit), ctypes.byref(group),
-                                                     self.NO_POSITION if position is None else int(position)))
-        self._grid_limit = int(grid_limit)
-        return int(group.value)
+        return self._debug_config_tile(grid_limit, position)
 
 
 class IfFirSynth(_StreamCtx):
     """One if_fir_synth_t: `channels` channel streams on a uniform grid to one IQ stream in one pass, `hop` output samples per
     frame of `bins` values (docs/SPEC.md §14).  Methods mirror the C entry points; its input is what IfFirPfb.process returns."""
-    _PREFIX = "if_fir_synth_"
-    NO_POSITION = (1 << 64) - 1
+    _FAMILY = "synth"
     ROUTE_PLAN, ROUTE_WORKSPACE, ROUTE_LDS = 0, 1, 2
 
     def __init__(self, taps, channels, hop=None, first_bin=0, bins=None, max_frames=1 << 12, device=0, dev=False):
-        self._L = dev_lib() if dev else lib()
-        self._ctx = ctypes.c_void_p()
-        self._dev = bool(dev)
+        self._open(dev)
         taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
         self.taps = taps
         self.channels = int(channels)
         self.hop = self.channels if hop is None else int(hop)
         self.first_bin = int(first_bin)
         self.bins = self.channels if bins is None else int(bins)
-        self._i16 = False
         if not all(0 <= v < 1 << 32 for v in (self.channels, self.hop, self.bins)) or not -(1 << 31) <= self.first_bin < 1 << 31:
             raise IfFirError("if_fir_synth_init: channels, hop and bins must be unsigned, first_bin a 32-bit integer")
         cfg = SynthConfig(self.channels, self.hop, self.first_bin, self.bins)
-        if not self._L.if_fir_synth_init(ctypes.byref(self._ctx), ctypes.byref(cfg), _f32p(taps) if taps.size else None, taps.size,
-                                         int(max_frames), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
+        self._init("init", ctypes.byref(cfg), _f32p(taps) if taps.size else None, taps.size, int(max_frames), int(device))
 
     def sample_count(self, frames):
         """if_fir_synth_sample_count(): output samples of a call with `frames` frames at the current stream position."""
-        return int(self._L.if_fir_synth_sample_count(self._ctx, int(frames)))
-
-    def _frames_input(self, frames):
-        """(contiguous array, frame count) of a host (frames, bins) array: complex64 / interleaved float32, or int16 pairs after
-        set_input_format(INPUT_I16)"""
-        x, n = self._host_input(frames)
-        if n % self.bins:
-            raise IfFirError("if_fir_synth_process: %d elements are not whole frames of %d bins" % (n, self.bins))
-        return x, n // self.bins
+        return self._count("sample_count", frames)
 
     def process(self, frames):
         """if_fir_synth_process(): a host (frames, bins) array in (what IfFirPfb.process returns); interleaved float32 out."""
         x, f = self._frames_input(frames)
         out = np.empty(2 * f * self.hop, dtype=np.float32)
-        m = ctypes.c_uint64(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._L.if_fir_synth_process(self._ctx, ctypes.c_void_p(x.ctypes.data if f else dummy.ctypes.data),
-                                                 _f32p(out if out.size else dummy), f, ctypes.byref(m)))
-        assert m.value * 2 == out.size
+        m = self._process_host(x, out, f)
+        assert m * 2 == out.size
         return out
 
     def process_device(self, dev_in, dev_out, frames):
         """if_fir_synth_process_device(): raw device pointers (ints), asynchronous.  Returns the samples emitted."""
-        m = ctypes.c_uint64(0)
-        self._check(self._L.if_fir_synth_process_device(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
-                                                        int(frames), ctypes.byref(m)))
-        return int(m.value)
-
-    def _need_dev(self, name):
-        if not self._dev:
-            raise IfFirError("%s is in the development library only: construct with dev=True" % name)
+        return self._process_device(dev_in, dev_out, frames)
 
     def debug_config(self, grid_limit=0, route=0, position=None):
         """if_fir_debug_synth_config() (development library: construct with dev=True): at most grid_limit workgroups per kernel
         (0 = the launcher's choice); route 0 = the plan's choice, 1 = workspace, 2 = LDS (refused where it does not fit);
         position (optional) = the absolute index of the next call's first FRAME, with the history zeroed.  Returns the route in
         use."""
-        self._need_dev("if_fir_debug_synth_config")
         got = ctypes.c_uint32(0)
-        self._check(self._L.if_fir_debug_synth_config(self._ctx, int(grid_limit), int(route), ctypes.byref(got),
-                                                      self.NO_POSITION if position is None else int(position)))
+        self._check(self._debug("config")(self._ctx, int(grid_limit), int(route), ctypes.byref(got), self._position(position)))
         return int(got.value)
 
     def debug_workspace(self, nbytes=0):
         """if_fir_debug_synth_workspace() (development library): nbytes > 0 replaces the workspace by one of that budget.
         Returns the frames of a call one chunk emits the outputs of."""
-        self._need_dev("if_fir_debug_synth_workspace")
         got = ctypes.c_uint64(0)
-        self._check(self._L.if_fir_debug_synth_workspace(self._ctx, int(nbytes), ctypes.byref(got)))
+        self._check(self._debug("workspace")(self._ctx, int(nbytes), ctypes.byref(got)))
         return int(got.value)
 
 
-class IfFirRsynth(_StreamCtx):
+class IfFirRsynth(_OutputFormat, _StreamCtx):
     """One if_fir_rsynth_t: the `channels` / 2 + 1 distinct channels of a uniform grid to one REAL stream in one pass, `hop` real
     output samples per frame of `bins` values (docs/SPEC.md §18).  Methods mirror the C entry points; its input is what
     IfFirRpfb.process returns, its output float32 or (after set_output_format(OUTPUT_I16)) int16."""
-    _PREFIX = "if_fir_rsynth_"
-    NO_POSITION = (1 << 64) - 1
+    _FAMILY = "rsynth"
 
     def __init__(self, taps, channels, hop=None, first_bin=0, bins=None, max_frames=1 << 12, device=0, dev=False):
-        self._L = dev_lib() if dev else lib()
-        self._ctx = ctypes.c_void_p()
-        self._dev = bool(dev)
+        self._open(dev)
         taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
         self.taps = taps
         self.channels = int(channels)
         self.hop = self.channels if hop is None else int(hop)
         self.first_bin = int(first_bin)
         self.bins = self.channels // 2 + 1 - self.first_bin if bins is None else int(bins)
-        self._i16 = self._o16 = False
         if not all(0 <= v < 1 << 32 for v in (self.channels, self.hop, self.first_bin, self.bins)):
             raise IfFirError("if_fir_rsynth_init: channels, hop, first_bin and bins must be unsigned 32-bit integers")
         cfg = RsynthConfig(self.channels, self.hop, self.first_bin, self.bins)
-        if not self._L.if_fir_rsynth_init(ctypes.byref(self._ctx), ctypes.byref(cfg), _f32p(taps) if taps.size else None, taps.size,
-                                          int(max_frames), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
-
-    def set_output_format(self, fmt):
-        """if_fir_rsynth_set_output_format(): OUTPUT_F32 or OUTPUT_I16 (the float32 result times 2^15, to nearest even, saturated)."""
-        self._check(self._L.if_fir_rsynth_set_output_format(self._ctx, int(fmt)))
-        self._o16 = (int(fmt) == OUTPUT_I16)
+        self._init("init", ctypes.byref(cfg), _f32p(taps) if taps.size else None, taps.size, int(max_frames), int(device))
 
     def sample_count(self, frames):
         """if_fir_rsynth_sample_count(): output samples of a call with `frames` frames at the current stream position."""
-        return int(self._L.if_fir_rsynth_sample_count(self._ctx, int(frames)))
-
-    def _frames_input(self, frames):
-        """(contiguous array, frame count) of a host (frames, bins) array: complex64 / interleaved float32, or int16 pairs after
-        set_input_format(INPUT_I16)"""
-        x, n = self._host_input(frames)
-        if n % self.bins:
-            raise IfFirError("if_fir_rsynth_process: %d elements are not whole frames of %d bins" % (n, self.bins))
-        return x, n // self.bins
+        return self._count("sample_count", frames)
 
     def process(self, frames):
         """if_fir_rsynth_process(): a host (frames, bins) array in (what IfFirRpfb.process returns); real float32 (or int16 after
         set_output_format(OUTPUT_I16)) out."""
         x, f = self._frames_input(frames)
         out = np.empty(f * self.hop, dtype=np.int16 if self._o16 else np.float32)
-        m = ctypes.c_uint64(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._L.if_fir_rsynth_process(self._ctx, ctypes.c_void_p(x.ctypes.data if f else dummy.ctypes.data),
-                                                  ctypes.c_void_p(out.ctypes.data if out.size else dummy.ctypes.data), f, ctypes.byref(m)))
-        assert m.value == out.size
+        m = self._process_host(x, out, f, ctypes.c_void_p)
+        assert m == out.size
         return out
 
     def process_device(self, dev_in, dev_out, frames):
         """if_fir_rsynth_process_device(): raw device pointers (ints), asynchronous.  Returns the samples emitted."""
-        m = ctypes.c_uint64(0)
-        self._check(self._L.if_fir_rsynth_process_device(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
-                                                         int(frames), ctypes.byref(m)))
-        return int(m.value)
-
-    def _need_dev(self, name):
-        if not self._dev:
-            raise IfFirError("%s is in the development library only: construct with dev=True" % name)
+        return self._process_device(dev_in, dev_out, frames)
 
     def debug_config(self, grid_limit=0, position=None):
         """if_fir_debug_rsynth_config() (development library: construct with dev=True): at most grid_limit workgroups per kernel
         (0 = the launcher's choice); position (optional) = the absolute index of the next call's first FRAME, with the history
         zeroed."""
-        self._need_dev("if_fir_debug_rsynth_config")
-        self._check(self._L.if_fir_debug_rsynth_config(self._ctx, int(grid_limit), self.NO_POSITION if position is None else int(position)))
+        self._check(self._debug("config")(self._ctx, int(grid_limit), self._position(position)))
 
     def debug_workspace(self, nbytes=0):
         """if_fir_debug_rsynth_workspace() (development library): nbytes > 0 replaces the workspace by one of that budget.
         Returns the frames of a call one chunk emits the outputs of."""
-        self._need_dev("if_fir_debug_rsynth_workspace")
         got = ctypes.c_uint64(0)
-        self._check(self._L.if_fir_debug_rsynth_workspace(self._ctx, int(nbytes), ctypes.byref(got)))
+        self._check(self._debug("workspace")(self._ctx, int(nbytes), ctypes.byref(got)))
         return int(got.value)
 
 
-class IfFirSub(_StreamCtx):
+class IfFirSub(_BinNco, _StreamCtx):
     """One if_fir_sub_t: the second stage of a two-stage channelizer over frames of `bins` elements (what IfFirPfb.process
     returns and IfFirSynth.process takes): every bin filtered by its own row of `taps` (one row for all bins, or a (bins, T)
     array), decimated by `decimation` and mixed by its own NCO in one pass (docs/SPEC.md §15).  Methods mirror the C entry
-    points; how many frames a call emits depends on the stream position (frame_count)."""
-    _PREFIX = "if_fir_sub_"
-    NO_POSITION = (1 << 64) - 1
+    points; how many frames a call emits depends on the stream position (frame_count).  The NCO frequencies (set_nco) are in
+    cycles per input frame."""
+    _FAMILY = "sub"
 
     def __init__(self, taps, bins, decimation=1, max_frames=1 << 12, device=0, dev=False, tap_rows=None):
-        self._L = dev_lib() if dev else lib()
-        self._ctx = ctypes.c_void_p()
-        self._dev = bool(dev)
+        self._open(dev)
         taps = np.ascontiguousarray(taps, dtype=np.float32)
         self.bins = int(bins)
         self.decimation = int(decimation)
         self.tap_rows = int(tap_rows) if tap_rows is not None else (taps.shape[0] if taps.ndim == 2 else 1)
         self.taps = taps.reshape(-1)
         self.ntaps = self.taps.size // self.tap_rows if self.tap_rows > 0 else 0
-        self._i16 = False
         if not all(0 <= v < 1 << 32 for v in (self.bins, self.ntaps, self.tap_rows, self.decimation)):
             raise IfFirError("if_fir_sub_init: bins, taps, tap rows and decimation must be unsigned 32-bit integers")
         cfg = SubConfig(self.bins, self.ntaps, self.tap_rows, self.decimation)
-        if not self._L.if_fir_sub_init(ctypes.byref(self._ctx), ctypes.byref(cfg), _f32p(self.taps) if self.taps.size else None,
-                                       int(max_frames), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
-
-    def set_nco(self, freqs):
-        """if_fir_sub_set_nco(): `bins` frequencies in cycles per input frame, |f| <= 0.5; None sets every word to 0."""
-        if freqs is None:
-            self._check(self._L.if_fir_sub_set_nco(self._ctx, None))
-            return
-        f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
-        if f.size != self.bins:
-            raise IfFirError("if_fir_sub_set_nco: %d frequencies for %d bins" % (f.size, self.bins))
-        self._check(self._L.if_fir_sub_set_nco(self._ctx, f.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
-
-    def get_nco(self):
-        """if_fir_sub_get_nco(): the quantised frequencies in force, one per bin."""
-        f = np.zeros(self.bins, dtype=np.float64)
-        self._check(self._L.if_fir_sub_get_nco(self._ctx, f.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
-        return f
+        self._init("init", ctypes.byref(cfg), _f32p(self.taps) if self.taps.size else None, int(max_frames), int(device))
 
     def frame_count(self, frames):
         """if_fir_sub_frame_count(): output frames of a call with `frames` frames at the current stream position."""
-        return int(self._L.if_fir_sub_frame_count(self._ctx, int(frames)))
+        return self._count("frame_count", frames)
 
     def process(self, frames):
         """if_fir_sub_process(): a host (frames, bins) array in (complex64 / interleaved float32, or int16 pairs after
         set_input_format(INPUT_I16)); returns the (output frames, bins) complex64 array."""
-        x, n = self._host_input(frames)
-        if n % self.bins:
-            raise IfFirError("if_fir_sub_process: %d elements are not whole frames of %d bins" % (n, self.bins))
-        f = n // self.bins
+        x, f = self._frames_input(frames)
         out = np.empty((self.frame_count(f), self.bins), dtype=np.complex64)
-        m = ctypes.c_uint64(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._L.if_fir_sub_process(self._ctx, ctypes.c_void_p(x.ctypes.data if f else dummy.ctypes.data),
-                                               _f32p(out.view(np.float32) if out.size else dummy), f, ctypes.byref(m)))
-        assert m.value == out.shape[0]
+        m = self._process_host(x, out, f)
+        assert m == out.shape[0]
         return out
 
     def process_device(self, dev_in, dev_out, frames):
         """if_fir_sub_process_device(): raw device pointers (ints), asynchronous.  Returns the frames emitted."""
-        m = ctypes.c_uint64(0)
-        self._check(self._L.if_fir_sub_process_device(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
-                                                      int(frames), ctypes.byref(m)))
-        return int(m.value)
+        return self._process_device(dev_in, dev_out, frames)
 
     def debug_config(self, grid_limit=0, position=None):
         """if_fir_debug_sub_config() (development library: construct with dev=True): at most grid_limit workgroups per kernel
         (0 = the launcher's choice); position (optional) = the absolute index of the next call's first FRAME, with the history
         zeroed.  Returns the (output, bin) values one tile holds."""
-        if not self._dev:
-            raise IfFirError("if_fir_debug_sub_config is in the development library only: construct with dev=True")
-        tile = ctypes.c_uint32(0)
-        self._check(self._L.if_fir_debug_sub_config(self._ctx, int(grid_limit), ctypes.byref(tile),
-                                                    self.NO_POSITION if position is None else int(position)))
-        return int(tile.value)
+        return self._debug_config_tile(grid_limit, position)
 
 
-class IfFirSubUp(_StreamCtx):
+class IfFirSubUp(_BinNco, _StreamCtx):
     """One if_fir_subup_t: the transmit mirror of IfFirSub over frames of `bins` elements (what IfFirSynth.process takes): every
     bin interpolated by `interpolation` through its own row of `taps` (one row for all bins, or a (bins, T) array) and mixed up
-    by its own NCO in one pass (docs/SPEC.md §16).  Methods mirror the C entry points; F frames in give F * interpolation out."""
-    _PREFIX = "if_fir_subup_"
-    NO_POSITION = (1 << 64) - 1
+    by its own NCO in one pass (docs/SPEC.md §16).  Methods mirror the C entry points; F frames in give F * interpolation out.
+    The NCO frequencies (set_nco) are in cycles per OUTPUT frame."""
+    _FAMILY = "subup"
 
     def __init__(self, taps, bins, interpolation=1, max_frames=1 << 12, device=0, dev=False, tap_rows=None):
-        self._L = dev_lib() if dev else lib()
-        self._ctx = ctypes.c_void_p()
-        self._dev = bool(dev)
+        self._open(dev)
         taps = np.ascontiguousarray(taps, dtype=np.float32)
         self.bins = int(bins)
         self.interpolation = int(interpolation)
         self.tap_rows = int(tap_rows) if tap_rows is not None else (taps.shape[0] if taps.ndim == 2 else 1)
         self.taps = taps.reshape(-1)
         self.ntaps = self.taps.size // self.tap_rows if self.tap_rows > 0 else 0
-        self._i16 = False
         if not all(0 <= v < 1 << 32 for v in (self.bins, self.ntaps, self.tap_rows, self.interpolation)):
             raise IfFirError("if_fir_subup_init: bins, taps, tap rows and interpolation must be unsigned 32-bit integers")
         cfg = SubUpConfig(self.bins, self.ntaps, self.tap_rows, self.interpolation)
-        if not self._L.if_fir_subup_init(ctypes.byref(self._ctx), ctypes.byref(cfg), _f32p(self.taps) if self.taps.size else None,
-                                         int(max_frames), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
-
-    def set_nco(self, freqs):
-        """if_fir_subup_set_nco(): `bins` frequencies in cycles per OUTPUT frame, |f| <= 0.5; None sets every word to 0."""
-        if freqs is None:
-            self._check(self._L.if_fir_subup_set_nco(self._ctx, None))
-            return
-        f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
-        if f.size != self.bins:
-            raise IfFirError("if_fir_subup_set_nco: %d frequencies for %d bins" % (f.size, self.bins))
-        self._check(self._L.if_fir_subup_set_nco(self._ctx, f.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
-
-    def get_nco(self):
-        """if_fir_subup_get_nco(): the quantised frequencies in force, one per bin."""
-        f = np.zeros(self.bins, dtype=np.float64)
-        self._check(self._L.if_fir_subup_get_nco(self._ctx, f.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
-        return f
+        self._init("init", ctypes.byref(cfg), _f32p(self.taps) if self.taps.size else None, int(max_frames), int(device))
 
     def frame_count(self, frames):
         """if_fir_subup_frame_count(): output frames of a call with `frames` frames (0 where the call would be refused)."""
-        return int(self._L.if_fir_subup_frame_count(self._ctx, int(frames)))
+        return self._count("frame_count", frames)
 
     def process(self, frames):
         """if_fir_subup_process(): a host (frames, bins) array in (complex64 / interleaved float32, or int16 pairs after
         set_input_format(INPUT_I16)); returns the (frames * interpolation, bins) complex64 array."""
-        x, n = self._host_input(frames)
-        if n % self.bins:
-            raise IfFirError("if_fir_subup_process: %d elements are not whole frames of %d bins" % (n, self.bins))
-        f = n // self.bins
+        x, f = self._frames_input(frames)
         out = np.empty((self.frame_count(f), self.bins), dtype=np.complex64)
-        m = ctypes.c_uint64(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._L.if_fir_subup_process(self._ctx, ctypes.c_void_p(x.ctypes.data if f else dummy.ctypes.data),
-                                                 _f32p(out.view(np.float32) if out.size else dummy), f, ctypes.byref(m)))
-        assert m.value == out.shape[0]
+        m = self._process_host(x, out, f)
+        assert m == out.shape[0]
         return out
 
     def process_device(self, dev_in, dev_out, frames):
         """if_fir_subup_process_device(): raw device pointers (ints), asynchronous.  Returns the frames emitted."""
-        m = ctypes.c_uint64(0)
-        self._check(self._L.if_fir_subup_process_device(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
-                                                        int(frames), ctypes.byref(m)))
-        return int(m.value)
+        return self._process_device(dev_in, dev_out, frames)
 
     def debug_config(self, grid_limit=0, position=None):
         """if_fir_debug_subup_config() (development library: construct with dev=True): at most grid_limit workgroups per
         kernel (0 = the launcher's choice); position (optional) = the absolute index of the next call's first INPUT frame, with
         the history zeroed.  Returns the (output, bin) values one tile holds."""
-        if not self._dev:
-            raise IfFirError("if_fir_debug_subup_config is in the development library only: construct with dev=True")
-        tile = ctypes.c_uint32(0)
-        self._check(self._L.if_fir_debug_subup_config(self._ctx, int(grid_limit), ctypes.byref(tile),
-                                                      self.NO_POSITION if position is None else int(position)))
-        return int(tile.value)
+        return self._debug_config_tile(grid_limit, position)
 
 
 FFT_TABLE_FLOATS = 2 * (4096 + 4096 + 256 + 1024 + 1024 + 64 + 256)
 
 
-class IfFirFpow(_StreamCtx):
+class IfFirFpow(_CodeFrames, _StreamCtx):
     """One if_fir_fpow_t: the power stage over frames of `bins` elements (what IfFirPfb, IfFirRpfb and IfFirSub emit): every
     output bin sums `group` adjacent elements from `first` on, every output frame averages `frames` input frames, and the result
     comes as the uint16 spectrum codes wb_detect reads and, optionally, as float32 powers (docs/SPEC.md §19).  Methods mirror
     the C entry points; how many frames a call emits depends on the stream position (frame_count)."""
-    _PREFIX = "if_fir_fpow_"
-    NO_POSITION = (1 << 64) - 1
+    _FAMILY = "fpow"
 
     def __init__(self, bins, frames, norm=1.0, first=0, group=1, out_bins=None, ref_power=1.0, input_format=INPUT_F32,
                  max_frames=1 << 12, device=0, dev=False):
-        self._L = dev_lib() if dev else lib()
-        self._ctx = ctypes.c_void_p()
-        self._dev = bool(dev)
+        self._open(dev)
         self.bins, self.first, self.group, self.frames = int(bins), int(first), int(group), int(frames)
         self.out_bins = int(out_bins) if out_bins is not None else (max(self.bins - self.first, 0) // self.group if self.group > 0 else 0)
         self._i16 = (int(input_format) == INPUT_I16)
         if not all(0 <= v < 1 << 32 for v in (self.bins, self.first, self.group, self.out_bins, self.frames, int(input_format))):
             raise IfFirError("if_fir_fpow_init: bins, first, group, output bins, frames and format must be unsigned 32-bit integers")
         cfg = FpowConfig(self.bins, self.first, self.group, self.out_bins, self.frames, float(norm), float(ref_power), int(input_format))
-        if not self._L.if_fir_fpow_init(ctypes.byref(self._ctx), ctypes.byref(cfg), int(max_frames), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
+        self._init("init", ctypes.byref(cfg), int(max_frames), int(device))
 
     def frame_count(self, frames):
         """if_fir_fpow_frame_count(): output frames of a call with `frames` input frames at the current stream position."""
-        return int(self._L.if_fir_fpow_frame_count(self._ctx, int(frames)))
+        return self._count("frame_count", frames)
 
     def process(self, frames, want_power=True):
         """if_fir_fpow_process(): a host (frames, bins) array in (complex64 / interleaved float32, or int16 pairs after
         set_input_format(INPUT_I16)); returns ((output frames, out_bins) uint16 codes, float32 powers of that shape or None)."""
-        x, n = self._host_input(frames)
-        if n % self.bins:
-            raise IfFirError("if_fir_fpow_process: %d elements are not whole frames of %d bins" % (n, self.bins))
-        f = n // self.bins
-        m_want = self.frame_count(f)
-        codes = np.empty((m_want, self.out_bins), dtype=np.uint16)
-        power = np.empty((m_want, self.out_bins), dtype=np.float32) if want_power else None
-        m = ctypes.c_uint32(0)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._L.if_fir_fpow_process(
-            self._ctx, ctypes.c_void_p(x.ctypes.data if f else dummy.ctypes.data), f,
-            codes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)) if m_want else None,
-            _f32p(power) if want_power and m_want else None, ctypes.byref(m)))
-        assert m.value == m_want
-        return codes, power
+        x, f = self._frames_input(frames)
+        return self._process_codes(x, f, self.frame_count(f), self.out_bins, want_power)
 
     def process_device(self, dev_in, frames, dev_bins, dev_power=0):
         """if_fir_fpow_process_device(): raw device pointers (ints; dev_power may be 0), asynchronous.  Returns the frames emitted."""
-        m = ctypes.c_uint32(0)
-        self._check(self._L.if_fir_fpow_process_device(self._ctx, ctypes.c_void_p(dev_in or None), int(frames),
-                                                       ctypes.c_void_p(dev_bins or None), ctypes.c_void_p(dev_power or None),
-                                                       ctypes.byref(m)))
-        return int(m.value)
+        return self._process_codes_device(dev_in, frames, dev_bins, dev_power)
 
     def debug_config(self, grid_limit=0, position=None):
         """if_fir_debug_fpow_config() (development library: construct with dev=True): at most grid_limit workgroups per kernel
         (0 = the launcher's choice); position (optional) = the absolute index of the next call's first input FRAME, with the
         carried sums cleared."""
-        if not self._dev:
-            raise IfFirError("if_fir_debug_fpow_config is in the development library only: construct with dev=True")
-        self._check(self._L.if_fir_debug_fpow_config(self._ctx, int(grid_limit),
-                                                     self.NO_POSITION if position is None else int(position)))
+        self._check(self._debug("config")(self._ctx, int(grid_limit), self._position(position)))
 
 
 TURN_TO_STREAMS, TURN_TO_FRAMES = 0, 1
 
 
-class IfFirTurn(_StreamCtx):
+class IfFirTurn(_OutputFormat, _StreamCtx):
     """One if_fir_turn_t: the corner turn between frames of `bins` elements (the layout of IfFirPfb, IfFirRpfb, IfFirSub, IfFirSubUp,
     IfFirSynth, IfFirRsynth and IfFirFpow) and one contiguous row per listed bin (what the stream families read and write), with
-    the format conversion fused (docs/SPEC.md §20).  `sel` is a list of distinct bins in any order, or None for the span
-    first .. first + channels - 1.  The stage carries no state: there is no reset.  Methods mirror the C entry points."""
-    _PREFIX = "if_fir_turn_"
+    the format conversion fused (docs/SPEC.md §20; for OUTPUT_I16 a NaN gives 0).  `sel` is a list of distinct bins in any order,
+    or None for the span first .. first + channels - 1.  The stage carries no state: there is no reset.  Methods mirror the C
+    entry points."""
+    _FAMILY = "turn"
 
     def __init__(self, direction, bins, sel=None, channels=None, first=0, input_format=INPUT_F32, output_format=OUTPUT_F32,
                  max_frames=1 << 12, device=0, dev=False):
-        self._L = dev_lib() if dev else lib()
-        self._ctx = ctypes.c_void_p()
-        self._dev = bool(dev)
+        self._open(dev)
         self.direction, self.bins, self.first = int(direction), int(bins), int(first)
         if sel is not None:
             sel = [int(v) for v in np.asarray(sel).reshape(-1)]
@@ -1797,54 +1390,41 @@ class IfFirTurn(_StreamCtx):
             raise IfFirError("if_fir_turn_init: %d listed bins for %d channels" % (len(sel), self.channels))
         cfg = TurnConfig(self.direction, self.bins, self.channels, self.first, int(input_format), int(output_format))
         arr = (ctypes.c_uint32 * max(len(sel), 1))(*sel) if sel is not None else None
-        if not self._L.if_fir_turn_init(ctypes.byref(self._ctx), ctypes.byref(cfg), arr, int(max_frames), int(device)):
-            self._ctx = ctypes.c_void_p()
-            raise IfFirError(self._c("last_error")(None).decode())
+        self._init("init", ctypes.byref(cfg), arr, int(max_frames), int(device))
         self.sel = list(sel) if sel is not None else list(range(self.first, self.first + self.channels))
 
     def reset(self):
         raise IfFirError("if_fir_turn_t carries no state: there is no reset")
-
-    def set_output_format(self, fmt):
-        """if_fir_turn_set_output_format(): OUTPUT_F32 or OUTPUT_I16 (times 2^15, to nearest even, saturated; NaN gives 0)."""
-        self._check(self._L.if_fir_turn_set_output_format(self._ctx, int(fmt)))
-        self._o16 = (int(fmt) == OUTPUT_I16)
 
     def process(self, data, pitch=None, frames=None):
         """if_fir_turn_process(): host arrays.  TO_STREAMS: a (frames, bins) array in (complex64 / interleaved float32, or int16
         pairs after set_input_format(INPUT_I16)), a (channels, pitch, 2) float32 or int16 array out (pitch: default frames), of
         which [:, :frames] is written and the rest is zero.  TO_FRAMES: a (channels, pitch) array of elements in, of which the
         first `frames` (default: pitch) of every row are used, a (frames, bins, 2) array out."""
-        x, n = self._host_input(data)
         odt = np.int16 if self._o16 else np.float32
         if self.direction == TURN_TO_FRAMES:
+            x, n = self._host_input(data)
             if n % self.channels:
                 raise IfFirError("if_fir_turn_process: %d elements are not %d rows" % (n, self.channels))
             p = n // self.channels
             f = p if frames is None else int(frames)
             out = np.zeros((max(f, 0), self.bins, 2), dtype=odt)
         else:
-            if n % self.bins:
-                raise IfFirError("if_fir_turn_process: %d elements are not whole frames of %d bins" % (n, self.bins))
-            f = n // self.bins
+            x, f = self._frames_input(data)
             p = f if pitch is None else int(pitch)
             out = np.zeros((self.channels, p, 2), dtype=odt)
-        dummy = np.zeros(2, dtype=np.float32)
-        self._check(self._L.if_fir_turn_process(self._ctx, ctypes.c_void_p(x.ctypes.data if x.size else dummy.ctypes.data),
-                                                ctypes.c_void_p(out.ctypes.data if out.size else dummy.ctypes.data), f, p))
+        self._check(self._c("process")(self._ctx, _host_ptr(x), _host_ptr(out), f, p))
         return out
 
     def process_device(self, dev_in, dev_out, frames, pitch=None):
         """if_fir_turn_process_device(): raw device pointers (ints), asynchronous; pitch in elements (default: frames)."""
-        self._check(self._L.if_fir_turn_process_device(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
-                                                       int(frames), int(frames if pitch is None else pitch)))
+        self._check(self._process_device_c(self._ctx, ctypes.c_void_p(dev_in or None), ctypes.c_void_p(dev_out or None),
+                                           int(frames), int(frames if pitch is None else pitch)))
 
     def debug_config(self, grid_limit=0):
         """if_fir_debug_turn_config() (development library: construct with dev=True): at most grid_limit workgroups (0 = the
         launcher's choice)."""
-        if not self._dev:
-            raise IfFirError("if_fir_debug_turn_config is in the development library only: construct with dev=True")
-        self._check(self._L.if_fir_debug_turn_config(self._ctx, int(grid_limit)))
+        self._check(self._debug("config")(self._ctx, int(grid_limit)))
 
 
 def debug_fft_tables(taps, decimation, complex_taps=False, nco_delta=0):
@@ -1866,10 +1446,7 @@ def debug_fft_tables_bank(taps, bank, parity=0, complex_taps=False):
     taps = np.ascontiguousarray(taps, dtype=np.float32)
     t = taps.size // 2 if complex_taps else taps.size
     out = np.zeros(FFT_TABLE_FLOATS, dtype=np.float32)
-    L = dev_lib()
-    L.if_fir_debug_fft_tables_bank.restype = ctypes.c_uint32
-    n = L.if_fir_debug_fft_tables_bank(_f32p(taps), ctypes.c_uint32(t), ctypes.c_uint32(1 if complex_taps else 0), ctypes.c_uint32(int(bank)),
-                                       ctypes.c_uint32(int(parity)), _f32p(out), ctypes.c_uint32(out.size))
+    n = dev_lib().if_fir_debug_fft_tables_bank(_f32p(taps), t, 1 if complex_taps else 0, int(bank), int(parity), _f32p(out), out.size)
     if n != FFT_TABLE_FLOATS:
         raise IfFirError("if_fir_debug_fft_tables_bank: (taps=%d, bank=%d) is not served" % (t, bank))
     c = out.view(np.complex64)
@@ -1878,9 +1455,7 @@ def debug_fft_tables_bank(taps, bank, parity=0, complex_taps=False):
 
 def debug_bank_tail(decimation, own_centres=False):
     """if_fir_debug_bank_tail(): the bank's tail (4, 8, 16) for a decimation, 0 if the bank does not serve it."""
-    L = dev_lib()
-    L.if_fir_debug_bank_tail.restype = ctypes.c_uint32
-    return int(L.if_fir_debug_bank_tail(ctypes.c_uint32(int(decimation)), ctypes.c_uint32(1 if own_centres else 0)))
+    return int(dev_lib().if_fir_debug_bank_tail(int(decimation), 1 if own_centres else 0))
 
 
 def debug_bank8_plan(slots):
@@ -1888,9 +1463,7 @@ def debug_bank8_plan(slots):
     k = len(slots)
     arr = (ctypes.c_uint32 * k)(*[int(v) for v in slots])
     out = (ctypes.c_uint32 * 3)()
-    L = dev_lib()
-    L.if_fir_debug_bank_plan.restype = ctypes.c_uint8
-    if not L.if_fir_debug_bank_plan(arr, ctypes.c_uint32(k), out):
+    if not dev_lib().if_fir_debug_bank_plan(arr, k, out):
         raise IfFirError("if_fir_debug_bank_plan: 1..16 channels")
     return int(out[0]), int(out[1]), [c for c in range(k) if (out[2] >> c) & 1]
 
@@ -1901,11 +1474,8 @@ def debug_fft_tables_odd(taps, decimation, complex_taps=False, nco_delta=0):
     t = taps.size // 2 if complex_taps else taps.size
     nfl = 10496 + 512
     out = np.zeros(nfl, dtype=np.float32)
-    L = dev_lib()
-    L.if_fir_debug_fft_tables_odd.restype = ctypes.c_uint32
-    n = L.if_fir_debug_fft_tables_odd(_f32p(taps), ctypes.c_uint32(t), ctypes.c_uint32(1 if complex_taps else 0),
-                                      ctypes.c_uint32(int(decimation)), ctypes.c_uint32(int(nco_delta) & 0xFFFFFFFF), _f32p(out),
-                                      ctypes.c_uint32(out.size))
+    n = dev_lib().if_fir_debug_fft_tables_odd(_f32p(taps), t, 1 if complex_taps else 0, int(decimation), int(nco_delta) & 0xFFFFFFFF,
+                                              _f32p(out), out.size)
     if n != nfl:
         raise IfFirError("if_fir_debug_fft_tables_odd: (taps=%d, decimation=%d) is not served by the odd-decimation kernel" % (t, decimation))
     c = out.view(np.complex64)
